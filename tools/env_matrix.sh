@@ -37,6 +37,6 @@ run PC_PIPELINE=0
 run PC_PIPELINE_DEC=0
 run PC_HOST_THREADS=1
 run PC_HYPER_PARALLEL=1 PC_NO_STREAMED_ENCODE=0
-run GPU_MAX_HW_QUEUES=16
+run GPU_MAX_HW_QUEUES=1
 echo "matrix failures: $fail"
 exit $fail
