@@ -5,12 +5,12 @@ Per image: centre zero-pad to a multiple of 64 (step.py:318-319, compressai.ops.
 for every level `p` of `pr_list`: compress -> decompress (only the decode is timed, step.py:332-340),
 un-pad and clamp (step.py:342-343), PSNR = -10 log10(mean((x - x_hat)^2)) (step.py:13-18,349),
 bpp = 8 * (sum of the byte-string lengths) / (H*W) over the UNPADDED size (step.py:357-365).
-File reading, wandb logging and the text dump of step.py are outside the hot path.
+Wandb logging and file reading of step.py are outside the hot path.
 
-Return signature: the reference returns (bpp, psnr, mssim, dec_time) per level (step.py:404); this harness returns
-(bpp, psnr, dec_time, rows) -- the MS-SSIM column (step.py:350-353, `pytorch_msssim.ms_ssim`) is NOT produced: that package is
-absent from this image and from the GPU box, the reference holds no MS-SSIM fixture, so any restatement would be parity-unpinned.
-Callers that need it can compute it from the x_hat of decompress() with their own MS-SSIM.
+Return signature: (bpp, psnr, dec_time) per level, as step.py:404 returns, plus the per-image table.  With ms_ssim=True every row also
+holds MS-SSIM (step.py:350-353: progressivecodec_amd.metrics.ms_ssim, data_range=1, on the same un-padded, clamped x_hat and original x
+as PSNR; outside every dec_time window) and its dB form -10 log10(1 - v) (step.py:351).  writing=<dir> appends the per-level text dump
+of step.py:370-374 / :397-403.
 """
 import math
 import time
@@ -83,8 +83,35 @@ def _pipeline_of(model):
     return pipe
 
 
+def _ms_ssim_of(x, x_hat):
+    """per-image MS-SSIM of a batch (one launch set, one read-back), as step.py:350 computes it per image"""
+    from .metrics import ms_ssim
+    return ms_ssim(x, x_hat, data_range=1., size_average=False).tolist()
+
+
+def _db(v):
+    """step.py:351: -10 log10(1 - v); inf at v = 1"""
+    return -10.0 * math.log10(1.0 - v) if v < 1.0 else float("inf")
+
+
+def _write_levels(writing, rows, pr_list, names):
+    """step.py:370-374 (one line per image, cheating=False bpp) and :397-403 (the level's averages): appended to
+    <writing>/level_<j>_.txt.  rows are image-major, levels in pr_list order."""
+    import os
+    n_lev = len(pr_list)
+    n_img = len(rows) // max(1, n_lev)
+    for j in range(n_lev):
+        mine = [rows[i * n_lev + j] for i in range(n_img)]
+        with open(os.path.join(writing, "level_" + str(j) + "_.txt"), "a+") as f:
+            for i, r in enumerate(mine):
+                name = str(names[i]) if names is not None else str(i)
+                f.write("SEQUENCE " + name + " BITS " + str(r["bpp"]) + " PSNR " + str(r["psnr"]) + " MSSIM " + str(r["ms_ssim_db"]) + "\n")
+            avg = lambda k: sum(r[k] for r in mine) / max(1, n_img)
+            f.write("SEQUENCE " + "AVG " + "BITS " + str(avg("bpp")) + " YPSNR " + str(avg("psnr")) + " YMSSIM " + str(avg("ms_ssim_db")) + "\n")
+
+
 def compress_with_ac(model, images, pr_list=None, mask_pol="point-based-std", device="cuda", shared_base=False, batch_same_size=False,
-                     overlap=False, group_size=18):
+                     overlap=False, group_size=18, ms_ssim=False, writing=None, names=None):
     """images: iterable of [1,3,H,W] (or [3,H,W]) float tensors in [0,1].
     Returns (bpp[level], psnr[level], dec_time[level]) averaged over the images, as step.py:404 does,
     plus the per-image table.
@@ -102,10 +129,15 @@ def compress_with_ac(model, images, pr_list=None, mask_pol="point-based-std", de
     images (default 18: with two levels in flight inside every multi-level call -- round 4 -- large jobs are the efficient ones; the
     overlap then hides one job's decode behind the next job's encode) and run through a CodecPipeline (progressivecodec_amd/pipeline.py) -- the decode of job i beside the encode of job i+1, on
     an encoder and a decoder object, two streams, two host threads.  `model` may be a CodecPipeline, or a loaded model around which
-    one is built on first use.  Same strings, same x_hat, same RD table; dec_time = the decode stream's time on the job / (images * levels)."""
+    one is built on first use.  Same strings, same x_hat, same RD table; dec_time = the decode stream's time on the job / (images * levels).
+
+    ms_ssim=True adds "ms_ssim" and "ms_ssim_db" to every row (step.py:350-353), in every path; the batched paths compute it with one
+    launch set and one read-back per (group, level).  writing=<dir> implies ms_ssim=True and appends level_<j>_.txt files in the line
+    formats of step.py:373 and :402; images are named names[i], or by their index when names is None."""
     import torch
     import torch.nn.functional as F
     pr_list = list(PR_LIST if pr_list is None else pr_list)
+    ms_ssim = ms_ssim or writing is not None
     rows = []
     if overlap:
         pipe = _pipeline_of(model)
@@ -137,12 +169,18 @@ def compress_with_ac(model, images, pr_list=None, mask_pol="point-based-std", de
                     x_hat = F.pad(out_dec["x_hat"], job["unpad"]).clamp_(0, 1)
                     y_strings, z_strings = data["strings"]
                     mses = torch.mean((xb - x_hat) ** 2, dim=(1, 2, 3)).tolist()
+                    msv = _ms_ssim_of(xb, x_hat) if ms_ssim else None
                     for b, i in enumerate(idxs):
                         nbytes = sum(len(s[b]) for s in y_strings) + len(z_strings[b])
-                        by_image.setdefault(i, []).append({"quality": p, "bpp": 8.0 * nbytes / (h * w),
-                                                           "psnr": -10.0 * math.log10(mses[b]) if mses[b] > 0 else float("inf"), "dec_time": dec_time})
+                        row = {"quality": p, "bpp": 8.0 * nbytes / (h * w),
+                               "psnr": -10.0 * math.log10(mses[b]) if mses[b] > 0 else float("inf"), "dec_time": dec_time}
+                        if ms_ssim:
+                            row.update(ms_ssim=msv[b], ms_ssim_db=_db(msv[b]))
+                        by_image.setdefault(i, []).append(row)
         for i in range(len(imgs)):
             rows.extend(by_image[i])
+        if writing is not None:
+            _write_levels(writing, rows, pr_list, names)
         n_img = max(1, len(imgs))
         avg = lambda key, p: sum(r[key] for r in rows if r["quality"] == p) / n_img
         return ([avg("bpp", p) for p in pr_list], [avg("psnr", p) for p in pr_list], [avg("dec_time", p) for p in pr_list], rows)
@@ -169,13 +207,19 @@ def compress_with_ac(model, images, pr_list=None, mask_pol="point-based-std", de
                     x_hat = F.pad(out_dec["x_hat"], unpad).clamp_(0, 1)
                     y_strings, z_strings = data["strings"]
                     mses = torch.mean((xb - x_hat) ** 2, dim=(1, 2, 3)).tolist()          # one reduction and one read-back per level, not per image
+                    msv = _ms_ssim_of(xb, x_hat) if ms_ssim else None
                     for b, i in enumerate(idxs):
                         mse = mses[b]
                         nbytes = sum(len(s[b]) for s in y_strings) + len(z_strings[b])
-                        by_image.setdefault(i, []).append({"quality": p, "bpp": 8.0 * nbytes / (h * w),
-                                                           "psnr": -10.0 * math.log10(mse) if mse > 0 else float("inf"), "dec_time": dec_time})
+                        row = {"quality": p, "bpp": 8.0 * nbytes / (h * w),
+                               "psnr": -10.0 * math.log10(mse) if mse > 0 else float("inf"), "dec_time": dec_time}
+                        if ms_ssim:
+                            row.update(ms_ssim=msv[b], ms_ssim_db=_db(msv[b]))
+                        by_image.setdefault(i, []).append(row)
         for i in range(len(imgs)):
             rows.extend(by_image[i])
+        if writing is not None:
+            _write_levels(writing, rows, pr_list, names)
         n_img = max(1, len(imgs))
         avg = lambda key, p: sum(r[key] for r in rows if r["quality"] == p) / n_img
         return ([avg("bpp", p) for p in pr_list], [avg("psnr", p) for p in pr_list], [avg("dec_time", p) for p in pr_list], rows)
@@ -202,6 +246,9 @@ def compress_with_ac(model, images, pr_list=None, mask_pol="point-based-std", de
                     y_strings, z_strings = data["strings"]
                     nbytes = sum(len(s[0]) for s in y_strings) + sum(len(s) for s in z_strings)
                     rows.append({"quality": p, "bpp": 8.0 * nbytes / (h * w), "psnr": psnr, "dec_time": dec_time})
+                    if ms_ssim:
+                        v = _ms_ssim_of(x, x_hat)[0]
+                        rows[-1].update(ms_ssim=v, ms_ssim_db=_db(v))
                 continue
             for p in pr_list:
                 data = model.compress(x_padded, quality=p, mask_pol=mask_pol)
@@ -218,6 +265,11 @@ def compress_with_ac(model, images, pr_list=None, mask_pol="point-based-std", de
                 y_strings, z_strings = data["strings"]
                 nbytes = sum(len(s[0]) for s in y_strings) + sum(len(s) for s in z_strings)   # step.py:357-365 (B = 1)
                 rows.append({"quality": p, "bpp": 8.0 * nbytes / (h * w), "psnr": psnr, "dec_time": dec_time})
+                if ms_ssim:
+                    v = _ms_ssim_of(x, x_hat)[0]
+                    rows[-1].update(ms_ssim=v, ms_ssim_db=_db(v))
+    if writing is not None:
+        _write_levels(writing, rows, pr_list, names)
     n_img = max(1, len(rows) // max(1, len(pr_list)))
     avg = lambda key, p: sum(r[key] for r in rows if r["quality"] == p) / n_img
     return ([avg("bpp", p) for p in pr_list], [avg("psnr", p) for p in pr_list], [avg("dec_time", p) for p in pr_list], rows)
