@@ -1128,6 +1128,8 @@ struct ChainCtx {
     int B, h, w, HW;
     size_t M;                                   // B * HW
     float *y, *lm, *ls, *yb, *ye, *mu, *scale, *thr, *masks;
+    const float *mu_base, *scale_base;          // set 0's per-slice mu / scale: the base half is written there only (second_level_set
+                                                // re-points mu / scale, not these)
     int32_t *sym, *idx;
     uint8_t* idx8;                              // decoder: byte copy of idx for the host coder
     int mode; float q; bool enh;
@@ -1243,8 +1245,8 @@ int rem_refine(const ChainCtx& k, int i, int b0, int nb, float* mu_i, float* sc_
     if (mode_star == 1) PCCHK(pc_quantile_thr_launch(sc_i, SLICE, nb, k.HW, SLICE, qs, thr2, qw, st));
     if (mode_bar == 1) PCCHK(pc_quantile_thr_launch(sc_i, SLICE, nb, k.HW, SLICE, qb, thr2 + k.B, qw, st));
     const float* yb_i = img(k.yb, b0, pi * D0) + 32 * i;
-    const float* mu_b = k.mu + (size_t)i * k.M * SLICE + (size_t)b0 * pi * SLICE;       // base step i: mu / scale kept per slice
-    const float* sd_b = k.scale + (size_t)i * k.M * SLICE + (size_t)b0 * pi * SLICE;
+    const float* mu_b = k.mu_base + (size_t)i * k.M * SLICE + (size_t)b0 * pi * SLICE;  // base step i: mu / scale kept per slice, in set 0
+    const float* sd_b = k.scale_base + (size_t)i * k.M * SLICE + (size_t)b0 * pi * SLICE;
     // f_ent_prog = enc_enh_entropy_params(scale), or of cat(mu, scale) in the mu_std form (:789)
     const float* x = sc_i; int ldx = SLICE;
     for (int j = 0; j < L.n_sub; ++j) {
@@ -1547,6 +1549,8 @@ bool pipeline_enabled(const pc_codec* c)
 // Second set of the level-specific buffers of a chain (decoded enhancement slices, per-slice mu / scale / symbols / indexes, mask
 // thresholds): with it the enhancement chains of TWO levels of a multi-level call run side by side -- they depend on the base slices
 // only (CHProg_cnn.py:775-845 / :930-983), never on each other.  Set 0 is the object's ordinary buffers (the taps tests read).
+// Only set 0 holds the base half of mu / scale (the base chain writes nothing else): a set-1 chain reads it through mu_base /
+// scale_base (the REM refinement, rem_refine), which are left pointing at set 0.
 int second_level_set(pc_codec* c, const ChainCtx& k, bool decoder, ChainCtx* k2)
 {
     *k2 = k;
@@ -1649,6 +1653,7 @@ int compress_impl(pc_codec* c, const float* x, int B, int H, int W, const double
     PCCHK(c->buf("sym", M * SLICE * 2 * NS0, &k.sym));
     PCCHK(c->buf("idx", M * SLICE * 2 * NS0, &k.idx));
     k.c = c; k.B = B; k.h = h; k.w = w; k.HW = HW; k.M = M;
+    k.mu_base = k.mu; k.scale_base = k.scale;
     k.cust_map = c->cust_map; c->cust_map = nullptr;
     k.rem_ckpt = c->rem_ckpt; c->rem_ckpt = nullptr;
 
@@ -1937,6 +1942,7 @@ extern "C" int pc_codec_forward(pc_codec* c, const float* x, int B, int H, int W
     PCCHK(c->buf("sym", M * SLICE * 2 * NS0, &k.sym));
     PCCHK(c->buf("idx", M * SLICE * 2 * NS0, &k.idx));
     k.c = c; k.B = B; k.h = h; k.w = w; k.HW = HW; k.M = M;
+    k.mu_base = k.mu; k.scale_base = k.scale;
     k.lik = y_lik; k.lik_nch = enh ? 2 * D0 : D0;
 
     PCCHK(g_a(c, st, x, B, H, W, k.y));                                                  // :1013
@@ -2018,6 +2024,7 @@ int decompress_impl(pc_codec* c, const uint8_t* const* y_strings, const size_t* 
     PCCHK(c->buf("idx", M * SLICE * 2 * NS0, &k.idx));
     PCCHK(c->buf("idx8", M * SLICE * 2 * NS0, &k.idx8));
     k.c = c; k.B = B; k.h = h; k.w = w; k.HW = HW; k.M = M;
+    k.mu_base = k.mu; k.scale_base = k.scale;
     k.cust_map = c->cust_map; c->cust_map = nullptr;
     k.rem_ckpt = c->rem_ckpt; c->rem_ckpt = nullptr;
     const size_t per = (size_t)SLICE * HW, per_z = (size_t)NCH * ZHW;

@@ -347,11 +347,11 @@ class ChannelProgresssiveWACNN(_module_base()):
 
     # ------------------------------------------------------------------ multi-level (shared base) coding
     @_one_call_at_a_time
-    def compress_levels(self, x, qualities, mask_pol=None):
+    def compress_levels(self, x, qualities, mask_pol=None, cust_map=None):
         """compress() for a list of mask levels with the level-independent part (g_a, h_a, z, h_s, the ten base slices;
         CHProg_cnn.py:692-767) computed once -- SURVEY.md section 8(f) rank 1.  Returns one compress()-style dictionary per
         level; the z strings and the ten base y strings are the same objects in every entry, and every entry equals what
-        compress(x, q, mask_pol) returns for that level."""
+        compress(x, q, mask_pol, cust_map) returns for that level (a cust_map applies to every level with quality > 0)."""
         import torch
         mask_pol = self.mask_policy if mask_pol is None else mask_pol
         if mask_pol not in _MASK_POL:
@@ -372,6 +372,7 @@ class ChannelProgresssiveWACNN(_module_base()):
         masks = [torch.empty((10, B, 32, h, w), device=self.device, dtype=torch.float32) if q > 0 else None for q in qualities]
         mp = (C.c_void_p * L)(*[m.data_ptr() if m is not None else None for m in masks])
         qa = (C.c_double * L)(*qualities)
+        cm = self._set_cust_map(cust_map if any(q > 0 for q in qualities) else None, B, h, w)   # kept alive through the call
         check(lib().pc_codec_compress_levels(self._h, C.c_void_p(x.data_ptr()), B, H, W, qa, L, _MASK_POL[mask_pol], mp, self._stream()),
               "pc_codec_compress_levels")
         strs = self._fetch_strings()                                             # slots [10 + 10*L][B], then z
@@ -386,11 +387,12 @@ class ChannelProgresssiveWACNN(_module_base()):
         return out
 
     @_one_call_at_a_time
-    def decompress_levels(self, strings_per_level, shape, qualities, mask_pol=None):
+    def decompress_levels(self, strings_per_level, shape, qualities, mask_pol=None, cust_map=None):
         """decompress() for a list of levels of the same images: z, h_s and the ten base slices are decoded once
         (CHProg_cnn.py:855-904), each level decodes its enhancement chain and runs its synthesis transform.
         strings_per_level[l] = [y_strings, z_strings] as returned by compress()/compress_levels() for level l (the base and z
-        strings are taken from entry 0).  Returns one {"x_hat"} dictionary per level, equal to decompress() of that level."""
+        strings are taken from entry 0).  Returns one {"x_hat"} dictionary per level, equal to decompress() of that level
+        (with the same cust_map, which applies to every level with quality != 0)."""
         import torch
         mask_pol = self.mask_policy if mask_pol is None else mask_pol
         if mask_pol not in _MASK_POL:
@@ -420,7 +422,9 @@ class ChannelProgresssiveWACNN(_module_base()):
                 slots += [[b""] * B for _ in range(10)]
         if any(len(sl) != B for sl in slots):
             raise ValueError("Invalid strings or indexes parameters")
+        cm = self._set_cust_map(cust_map if any(q != 0 for q in qualities) else None, B, 4 * zh, 4 * zw)
         x_hat = self._decompress_packed(slots, z_strings, B, zh, zw, qualities, mask_pol)
+        del cm
         return [{"x_hat": x_hat[lv]} for lv in range(L)]
 
     def read_latent(self, name, B, h, w):

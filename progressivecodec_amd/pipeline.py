@@ -117,7 +117,12 @@ class CodecPipeline:
     @classmethod
     def from_model(cls, model, queue_depth=2, n_pairs=1):
         """`model`: a loaded and updated ChannelProgresssiveWACNN -- it becomes the encoder; the decoder is a second object with the same
-        state dict (another 608 MB of HBM)."""
+        state dict (another 608 MB of HBM).  The REM model (PostRateProcessedNetwork) is refused: its refinement is switched on per call
+        on its base object, which the second (decoder) object would not carry -- overlap is not supported for REM."""
+        from .rem import PostRateProcessedNetwork
+        if isinstance(model, PostRateProcessedNetwork):
+            raise TypeError("CodecPipeline: overlap is not supported for the REM model (PostRateProcessedNetwork); "
+                            "use compress_with_ac(..., shared_base=True) or batch_same_size=True instead")
         if model._gc is None or model._eb is None:
             raise ValueError("Uninitialized CDFs. Run update() first")
         return cls(_encoder=model, queue_depth=queue_depth, n_pairs=n_pairs)

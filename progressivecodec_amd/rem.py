@@ -158,3 +158,27 @@ class PostRateProcessedNetwork(_module_base()):
         finally:
             self._off()
         return out
+
+    def compress_levels(self, x, qualities, mask_pol="point-based-std", checkpoint_rep=None):
+        """compress() for a list of levels with the level-independent part computed once (the base codec's compress_levels, with the
+        refinement on): entry l equals compress(x, qualities[l], mask_pol, checkpoint_rep) in "strings", "shape" and "masks".  There is
+        no "y_hat" entry: the codec's latent taps hold the buffers of one level only."""
+        if x.dim() != 4:
+            raise ValueError("Invalid `inputs` size. Expected a [B,3,H,W] tensor.")
+        self._on(checkpoint_rep, x.shape[0], x.shape[2] // 16, x.shape[3] // 16)
+        try:
+            return self.base_net.compress_levels(x, qualities, mask_pol)
+        finally:
+            self._off()
+
+    def decompress_levels(self, strings_per_level, shape, qualities, mask_pol=None, checkpoint_rep=None):
+        """decompress() for a list of levels of the same images (the base codec's decompress_levels, with the refinement on): entry l
+        equals decompress(strings_per_level[l], shape, qualities[l], mask_pol, checkpoint_rep) in "x_hat".  There is no "y_hat" entry:
+        the codec's latent taps hold the buffers of one level only."""
+        if not strings_per_level or not isinstance(strings_per_level[0], (tuple, list)) or len(strings_per_level[0]) != 2:
+            raise ValueError("Invalid `strings` parameter type.")
+        self._on(checkpoint_rep, len(strings_per_level[0][1]), 4 * int(shape[0]), 4 * int(shape[1]))
+        try:
+            return self.base_net.decompress_levels(strings_per_level, shape, qualities, mask_pol)
+        finally:
+            self._off()
