@@ -189,8 +189,8 @@ PC_API int pc_codec_set_threads(pc_codec* c, int n_threads);
  *   "host_threads"            as pc_codec_set_threads
  *   "profile_in_schedule" 0/1 1: pc_codec_profile_begin only brackets the launches and leaves the schedule alone (default 0: profiling
  *                             forces the serial schedule so that a launch's duration is its own)
- * Unknown names and out-of-range values return PC_ERR_ARG.  The tuning switches of the profiling rounds (PC_CONV_*, PC_LANES ...) exist
- * only in the -DPC_TUNING build of the library (csrc/Makefile `tuning`), not here. */
+ * Unknown names and out-of-range values return PC_ERR_ARG.  The conv kernel's tuning switches (PC_CONV_*) exist only in the -DPC_TUNING
+ * build of the library (csrc/Makefile `tuning`), not here. */
 PC_API int pc_codec_set_option(pc_codec* c, const char* name, int value);
 /* How the host entropy-coding pool of this process is laid out: threads = min(16, CPUs allowed by affinity and cgroup quota / local ranks),
  * pinned -- when there are several local ranks (LOCAL_WORLD_SIZE / LOCAL_RANK) -- to this rank's contiguous slice of the allowed CPUs

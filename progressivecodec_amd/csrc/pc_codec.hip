@@ -20,6 +20,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <mutex>
 #include <thread>
@@ -110,12 +111,8 @@ struct pc_codec {
     int res_slices = 0, res_B = 0;               // res_slices = string slots: 10 base + 10 per coded level
     std::vector<char> res_level_coded;            // per level of the last compress: enhancement strings present (quality > 0)
     std::vector<hipEvent_t> lvl_events;           // D2H completion of the base pass / of each level
-    hipStream_t copy_stream = nullptr;            // per-slice D2H of the last pass (streamed entropy coding)
     hipStream_t pipe_stream = nullptr;            // enhancement chain when it is pipelined against the base chain
-    hipStream_t hyper_streams[3] = {nullptr, nullptr, nullptr};   // the four hyper-synthesis nets run side by side
-    hipEvent_t hyper_ev[4] = {nullptr, nullptr, nullptr, nullptr};
     std::vector<hipEvent_t> pipe_ev;              // [NS0] base slice i complete, [NS0] pipeline fork, [NS0+1] pipeline join
-    std::vector<hipEvent_t> slice_ev;             // [2*NS0]: prep done / copied, per slice of that pass
     std::vector<std::vector<uint8_t>> y_strings;  // [slot*B + b]; slot = slice (base) or 10 + 10*level + (slice - 10)
     std::vector<std::vector<uint8_t>> z_strings;  // [b]
     int n_threads = 0;
@@ -129,8 +126,8 @@ struct pc_codec {
     double prof_flops = 0.0, prof_bytes = 0.0;
     struct ProfRec { int M, N, K, nphase, epi; double flops, bytes; double t0_ms, t1_ms; };   // t0 / t1: against the process epoch (pc_profile_set_epoch)
     std::vector<ProfRec> prof_rec;
-    // slice-chain lanes: one pair of non-blocking streams per sub-batch
-    struct Lane { hipStream_t sA = nullptr, sB = nullptr; hipEvent_t eA = nullptr, eB = nullptr, eDone = nullptr; };
+    // slice-chain lanes: one non-blocking stream per sub-batch
+    struct Lane { hipStream_t sA = nullptr; hipEvent_t eDone = nullptr; };
     std::vector<Lane> lanes;
     hipEvent_t eFork = nullptr;
     std::mutex buf_mu;
@@ -141,7 +138,7 @@ struct pc_codec {
     // last-call geometry for taps
     int last_B = 0, last_h16 = 0, last_w16 = 0;
 
-    template <typename T> int buf(const std::string& name, size_t count, T** out, bool zero_when_allocated = false)
+    template <typename T> int buf(const std::string& name, size_t count, T** out)
     {
         std::lock_guard<std::mutex> lk(buf_mu);
         DevBuf& d = bufs[name];
@@ -151,7 +148,6 @@ struct pc_codec {
             d.p = nullptr; d.bytes = 0;
             HIPCHK(hipMalloc(&d.p, need));
             d.bytes = need;
-            if (zero_when_allocated) { HIPCHK(hipMemset(d.p, 0, need)); HIPCHK(hipStreamSynchronize(nullptr)); }   // once per size: scratch whose kernels keep it zero between launches (the lanes' streams are non-blocking: the fill must have landed before one of them uses the buffer)
         }
         *out = reinterpret_cast<T*>(d.p);
         return PC_OK;
@@ -527,14 +523,14 @@ int stack5_pair(pc_codec* c, hipStream_t st, const Stack5W& sm, const Stack5W& s
 }
 
 // hyper-synthesis net (CHProg_cnn.py:208-232): z_hat [B][zh][zw][192] -> out slice [B][4zh][4zw][320] (ld 640)
-int hs(pc_codec* c, hipStream_t st, const HsW& h, const float* z, int B, int zh, int zw, float* out, int ldo, const char* tag = "")
+int hs(pc_codec* c, hipStream_t st, const HsW& h, const float* z, int B, int zh, int zw, float* out, int ldo)
 {
     const size_t M = (size_t)B * zh * zw;
     float *t0, *t1, *t2, *t3;
-    PCCHK(c->buf(std::string("hs_t0") + tag, M * 192, &t0));
-    PCCHK(c->buf(std::string("hs_t1") + tag, M * 4 * 224, &t1));
-    PCCHK(c->buf(std::string("hs_t2") + tag, M * 4 * 256, &t2));
-    PCCHK(c->buf(std::string("hs_t3") + tag, M * 16 * 288, &t3));
+    PCCHK(c->buf("hs_t0", M * 192, &t0));
+    PCCHK(c->buf("hs_t1", M * 4 * 224, &t1));
+    PCCHK(c->buf("hs_t2", M * 4 * 256, &t2));
+    PCCHK(c->buf("hs_t3", M * 16 * 288, &t3));
     PCCHK(conv(st, h.c0, {{z, 192, 192}}, B, zh, zw, 1, t0, 192, PC_EPI_GELU));
     PCCHK(conv(st, h.c2, {{t0, 192, 192}}, B, zh, zw, 1, t1, 224, PC_EPI_GELU, nullptr, 0, nullptr, 0, true));
     PCCHK(conv(st, h.c4, {{t1, 224, 224}}, B, 2 * zh, 2 * zw, 1, t2, 256, PC_EPI_GELU));
@@ -663,35 +659,15 @@ int mask_mode_for(int mask_pol, double quality, float* q_out)
 
 int hyper(pc_codec* c, hipStream_t st, const float* z_hat, int B, int zh, int zw, double quality, float* lm, float* ls)
 {
-    // h_scale_s[k] / h_mean_s[k] (CHProg_cnn.py:705-715) all read z_hat and nothing else: their first layers have ~110 workgroups
-    // each on 256 CUs, so the two (base only) or four nets CAN run side by side on their own streams with their own workspaces
-    // (PC_HYPER_PARALLEL=1).  That was worth 1 % in round 1; with the encoder / decoder objects side by side and the chains pipelined it costs
-    // 3 % of the overlapped bench and 2-5 % of the sequential one (profiles/r03_t_hyper_parallel_ab.log): four more streams' launches in a
-    // chip that is already shared by four chains.  Default off since round 3.
-    static const bool par = pc_tune("PC_HYPER_PARALLEL", 0) != 0;
-    const int n = quality != 0 ? 4 : 2;
-    if (!par || c->serial_profile() || c->opt_serial) {
-        PCCHK(hs(c, st, c->hss[0], z_hat, B, zh, zw, ls, MLAT));
-        PCCHK(hs(c, st, c->hms[0], z_hat, B, zh, zw, lm, MLAT));
-        if (quality != 0) {                       // CHProg_cnn.py:708-715
-            PCCHK(hs(c, st, c->hss[1], z_hat, B, zh, zw, ls + D0, MLAT));
-            PCCHK(hs(c, st, c->hms[1], z_hat, B, zh, zw, lm + D0, MLAT));
-        }
-        return PC_OK;
-    }
-    if (!c->hyper_ev[0]) {
-        for (auto& sx : c->hyper_streams) HIPCHK(hipStreamCreateWithFlags(&sx, hipStreamNonBlocking));
-        for (auto& e : c->hyper_ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    }
-    const HsW* nets[4] = {&c->hss[0], &c->hms[0], &c->hss[1], &c->hms[1]};
-    float* outs[4] = {ls, lm, ls + D0, lm + D0};
-    const char* tags[4] = {"", "_h1", "_h2", "_h3"};
-    HIPCHK(hipEventRecord(c->hyper_ev[0], st));                                         // fork: z_hat ready
-    for (int i = 0; i < n; ++i) {
-        hipStream_t sx = i == 0 ? st : c->hyper_streams[i - 1];
-        if (i > 0) HIPCHK(hipStreamWaitEvent(sx, c->hyper_ev[0], 0));
-        PCCHK(hs(c, sx, *nets[i], z_hat, B, zh, zw, outs[i], MLAT, tags[i]));
-        if (i > 0) { HIPCHK(hipEventRecord(c->hyper_ev[i], sx)); HIPCHK(hipStreamWaitEvent(st, c->hyper_ev[i], 0)); }   // join
+    // h_scale_s[k] / h_mean_s[k] (CHProg_cnn.py:705-715) all read z_hat and nothing else, one after the other on `st`.  Running the two
+    // (base only) or four nets side by side on streams of their own was worth 1 % in round 1; with the encoder / decoder objects side
+    // by side and the chains pipelined it cost 3 % of the overlapped bench and 2-5 % of the sequential one
+    // (profiles/r03_t_hyper_parallel_ab.log): four more streams' launches in a chip that is already shared by four chains.  Removed.
+    PCCHK(hs(c, st, c->hss[0], z_hat, B, zh, zw, ls, MLAT));
+    PCCHK(hs(c, st, c->hms[0], z_hat, B, zh, zw, lm, MLAT));
+    if (quality != 0) {                           // CHProg_cnn.py:708-715
+        PCCHK(hs(c, st, c->hss[1], z_hat, B, zh, zw, ls + D0, MLAT));
+        PCCHK(hs(c, st, c->hms[1], z_hat, B, zh, zw, lm + D0, MLAT));
     }
     return PC_OK;
 }
@@ -856,16 +832,12 @@ extern "C" void pc_codec_destroy(pc_codec* c)
     for (void* p : c->weight_allocs) (void)hipFree(p);
     for (auto& kv : c->bufs) if (kv.second.p) (void)hipFree(kv.second.p);
     for (hipEvent_t e : c->ev) (void)hipEventDestroy(e);
-    for (auto& L : c->lanes) { (void)hipStreamDestroy(L.sA); (void)hipStreamDestroy(L.sB); (void)hipEventDestroy(L.eA); (void)hipEventDestroy(L.eB); (void)hipEventDestroy(L.eDone); }
+    for (auto& L : c->lanes) { (void)hipStreamDestroy(L.sA); (void)hipEventDestroy(L.eDone); }
     if (c->eFork) (void)hipEventDestroy(c->eFork);
     if (c->call_done) (void)hipEventDestroy(c->call_done);
     if (c->staging_done) (void)hipEventDestroy(c->staging_done);
     for (hipEvent_t e : c->lvl_events) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->slice_ev) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->pipe_ev) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->hyper_ev) if (e) (void)hipEventDestroy(e);
-    for (hipStream_t sx : c->hyper_streams) if (sx) (void)hipStreamDestroy(sx);
-    if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     if (c->pipe_stream) (void)hipStreamDestroy(c->pipe_stream);
     if (c->h_sym) (void)hipHostFree(c->h_sym);
     if (c->h_idx) (void)hipHostFree(c->h_idx);
@@ -1101,12 +1073,11 @@ extern "C" int pc_codec_get_string(const pc_codec* c, int slice, int b, const ui
 
 // ---------------------------------------------------------------------------------------------- slice chain
 // The 20-step chain is serial per image but independent across images, and inside a step the mean and
-// scale stacks are independent.  Its GEMMs are small (M = B*h*w rows), so the chain is run as `n_lanes`
-// sub-batches, each on its own pair of non-blocking HIP streams (mean/prep/LRP on sA, scale (+quantile) on
-// sB, joined with events): up to 2*n_lanes kernels are resident at once and fill the MFMA pipes that one
-// such kernel leaves ~50 % idle; in the decoder each lane is driven by its own host thread, so one lane's
-// host rANS round trip overlaps the other lanes' GPU work.  Results do not depend on the split
-// (numeric contract: no cross-image arithmetic), which tests/test_gpu_codec.py checks.
+// scale stacks are independent: they run as one grouped launch per layer (stack5_pair).  Its GEMMs are small
+// (M = B*h*w rows), so the chain can run as `n_lanes` sub-batches, each on its own non-blocking HIP stream;
+// in the decoder each lane is driven by its own host thread, so one lane's host rANS round trip overlaps the
+// other lanes' GPU work.  Results do not depend on the split (numeric contract: no cross-image arithmetic),
+// which tests/test_gpu_codec.py checks.
 namespace {
 
 #define PC_DEFAULT_LANES_ENC 1
@@ -1132,7 +1103,7 @@ struct ChainCtx {
                                                 // re-points mu / scale, not these)
     int32_t *sym, *idx;
     uint8_t* idx8;                              // decoder: byte copy of idx for the host coder
-    int mode; float q; bool enh;
+    int mode; float q;
     double quality; int mask_pol;               // REM: the level being coded and the caller's mask policy (range / attention-mask selection)
     int step0, step1;                           // chain steps to run: [0,10) base, [10,20) enhancement
     int level;                                  // enhancement strings of this level sit at slot 10 + 10*level + i
@@ -1144,8 +1115,6 @@ struct ChainCtx {
     hipEvent_t* waitv;                          // if set: slice i of this pass starts only after waitv[i] (recorded by the other chain)
     SliceSignal* wait_count;                    //         host side: do not look at waitv[i] before it has been recorded
     size_t h_off;                               // decoder: offset (int32 units) of this chain's region in the pinned staging buffers
-    int32_t *so_sym, *so_idx;                   // streamed pass (single lane): pinned destinations; slice i of the pass is copied to
-                                                // so_sym + i*M*SLICE on c->copy_stream as soon as its prep kernel is done
 };
 
 template <typename T> inline T* img(T* p, int b0, size_t per_image) { return p ? p + (size_t)b0 * per_image : nullptr; }
@@ -1155,9 +1124,6 @@ int ensure_lanes(pc_codec* c, int n)
     while ((int)c->lanes.size() < n) {
         pc_codec::Lane L;
         HIPCHK(hipStreamCreateWithFlags(&L.sA, hipStreamNonBlocking));
-        HIPCHK(hipStreamCreateWithFlags(&L.sB, hipStreamNonBlocking));
-        HIPCHK(hipEventCreateWithFlags(&L.eA, hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&L.eB, hipEventDisableTiming));
         HIPCHK(hipEventCreateWithFlags(&L.eDone, hipEventDisableTiming));
         c->lanes.push_back(L);
     }
@@ -1167,12 +1133,9 @@ int ensure_lanes(pc_codec* c, int n)
 
 int lane_count(const pc_codec* c, int B, bool decode)
 {
-    static const int env = (int)pc_tune("PC_LANES", 0);
-    static const int env_e = (int)pc_tune("PC_LANES_ENC", 0);
-    static const int env_d = (int)pc_tune("PC_LANES_DEC", 0);
     // Config 2, round-1 final kernels (enc / dec ms per batch): lanes 1/1 35.9 / 36.4, 1/2 35.7 / 35.2, 2/2 37.1 / 36.0 -- the
     // encoder's GEMMs fill the chip best undivided; in the decoder a second lane hides the other lane's host rANS round trips
-    int n = decode ? (env_d > 0 ? env_d : (env > 0 ? env : PC_DEFAULT_LANES_DEC)) : (env_e > 0 ? env_e : (env > 0 ? env : PC_DEFAULT_LANES_ENC));
+    int n = decode ? PC_DEFAULT_LANES_DEC : PC_DEFAULT_LANES_ENC;
     if (decode ? c->opt_lanes_dec > 0 : c->opt_lanes_enc > 0) n = decode ? c->opt_lanes_dec : c->opt_lanes_enc;      // pc_codec_set_option
     if (c->serial_profile() || c->opt_serial) n = 1;
     return std::max(1, std::min(n, std::min(B, 8)));
@@ -1291,9 +1254,9 @@ int rem_refine(const ChainCtx& k, int i, int b0, int nb, float* mu_i, float* sc_
     return pc_rem_combine_launch(x, SLICE, sc_i, SLICE, nb, k.HW, thr2, mode_star, thr2 + k.B, mode_bar, st);
 }
 
-// mean / scale stacks (+ quantile threshold) of chain step `step` (0..9 base, 10..19 enhancement) for images [b0, b0+nb)
-int chain_params(const ChainCtx& k, int step, int b0, int nb, hipStream_t sA, hipStream_t sB, hipEvent_t eA, hipEvent_t eB,
-                 const std::string& tag)
+// mean / scale stacks (+ quantile threshold) of chain step `step` (0..9 base, 10..19 enhancement) for images [b0, b0+nb), as one
+// grouped launch per layer: mean (z = 0) and scale (z = 1)
+int chain_params(const ChainCtx& k, int step, int b0, int nb, hipStream_t st, const std::string& tag)
 {
     pc_codec* c = k.c;
     const size_t pi = (size_t)k.HW;             // pixels per image
@@ -1301,36 +1264,16 @@ int chain_params(const ChainCtx& k, int step, int b0, int nb, hipStream_t sA, hi
     float* yb = img(k.yb, b0, pi * D0); float* ye = img(k.ye, b0, pi * D0);
     float* mu_i = k.mu + (size_t)step * k.M * SLICE + (size_t)b0 * pi * SLICE;
     float* sc_i = k.scale + (size_t)step * k.M * SLICE + (size_t)b0 * pi * SLICE;
-    static const bool grouped = pc_tune("PC_GROUPED", 1) != 0;
     const std::string tm = "s5m" + tag, ts = "s5s" + tag;
-    if (grouped) {   // one grouped launch per layer: mean (z = 0) and scale (z = 1)
-        if (step < NS0) {
-            const int i = step, ns = std::min(5, i);
-            PCCHK(stack5_pair(c, sA, c->cc_mean[i], c->cc_scale[i], {{lm, MLAT, D0}, {yb, D0, 32 * ns}}, ls, nb, k.h, k.w, mu_i, sc_i, tm.c_str(), ts.c_str()));
-        } else {
-            const int i = step - NS0, s = std::min(5, i);
-            PCCHK(stack5_pair(c, sA, c->cc_mean_p[i], c->cc_scale_p[i], {{lm + D0, MLAT, D0}, {yb + 32 * i, D0, 32}, {ye + 32 * (i - s), D0, 32 * s}},
-                              ls + D0, nb, k.h, k.w, mu_i, sc_i, tm.c_str(), ts.c_str()));
-            PCCHK(rem_refine(k, i, b0, nb, mu_i, sc_i, sA, tag));                           // REM: refined scale before the mask (CHProgREM.py:812-826)
-            if (k.mode == 1) PCCHK(mask_threshold(k, i, b0, nb, sc_i, sA, tag));
-        }
-        return PC_OK;
-    }
-    const bool two = sB != sA;
-    if (two) { HIPCHK(hipEventRecord(eA, sA)); HIPCHK(hipStreamWaitEvent(sB, eA, 0)); }
     if (step < NS0) {
         const int i = step, ns = std::min(5, i);
-        PCCHK(stack5(c, sA, c->cc_mean[i], {{lm, MLAT, D0}, {yb, D0, 32 * ns}}, nb, k.h, k.w, mu_i, SLICE, PC_EPI_NONE, nullptr, 0, nullptr, 0, tm.c_str()));
-        PCCHK(stack5(c, sB, c->cc_scale[i], {{ls, MLAT, D0}, {yb, D0, 32 * ns}}, nb, k.h, k.w, sc_i, SLICE, PC_EPI_NONE, nullptr, 0, nullptr, 0, ts.c_str()));
-    } else {
-        const int i = step - NS0, s = std::min(5, i);
-        PCCHK(stack5(c, sA, c->cc_mean_p[i], {{lm + D0, MLAT, D0}, {yb + 32 * i, D0, 32}, {ye + 32 * (i - s), D0, 32 * s}}, nb, k.h, k.w, mu_i, SLICE, PC_EPI_NONE, nullptr, 0, nullptr, 0, tm.c_str()));
-        PCCHK(stack5(c, sB, c->cc_scale_p[i], {{ls + D0, MLAT, D0}, {yb + 32 * i, D0, 32}, {ye + 32 * (i - s), D0, 32 * s}}, nb, k.h, k.w, sc_i, SLICE, PC_EPI_NONE, nullptr, 0, nullptr, 0, ts.c_str()));
-        if (two && c->rem_n && c->rem_mu_std) { HIPCHK(hipEventRecord(eA, sA)); HIPCHK(hipStreamWaitEvent(sB, eA, 0)); }   // the refinement reads (and rewrites) mu, which stream A has just produced
-        PCCHK(rem_refine(k, i, b0, nb, mu_i, sc_i, sB, tag));
-        if (k.mode == 1) PCCHK(mask_threshold(k, i, b0, nb, sc_i, sB, tag));   // :819-824
+        return stack5_pair(c, st, c->cc_mean[i], c->cc_scale[i], {{lm, MLAT, D0}, {yb, D0, 32 * ns}}, ls, nb, k.h, k.w, mu_i, sc_i, tm.c_str(), ts.c_str());
     }
-    if (two) { HIPCHK(hipEventRecord(eB, sB)); HIPCHK(hipStreamWaitEvent(sA, eB, 0)); }
+    const int i = step - NS0, s = std::min(5, i);
+    PCCHK(stack5_pair(c, st, c->cc_mean_p[i], c->cc_scale_p[i], {{lm + D0, MLAT, D0}, {yb + 32 * i, D0, 32}, {ye + 32 * (i - s), D0, 32 * s}},
+                      ls + D0, nb, k.h, k.w, mu_i, sc_i, tm.c_str(), ts.c_str()));
+    PCCHK(rem_refine(k, i, b0, nb, mu_i, sc_i, st, tag));                               // REM: refined scale before the mask (CHProgREM.py:812-826)
+    if (k.mode == 1) PCCHK(mask_threshold(k, i, b0, nb, sc_i, st, tag));               // :819-824
     return PC_OK;
 }
 
@@ -1353,7 +1296,7 @@ int chain_lrp(const ChainCtx& k, int step, int b0, int nb, hipStream_t sA, const
                   ye + 32 * i, D0, PC_EPI_LRP_ADD, ye + 32 * i, D0, yb + 32 * i, D0, tm.c_str());
 }
 
-int encode_lane(const ChainCtx& k, int b0, int nb, hipStream_t sA, hipStream_t sB, hipEvent_t eA, hipEvent_t eB, const std::string& tag)
+int encode_lane(const ChainCtx& k, int b0, int nb, hipStream_t sA, const std::string& tag)
 {
     pc_codec* c = k.c;
     const size_t pi = (size_t)k.HW;
@@ -1363,7 +1306,7 @@ int encode_lane(const ChainCtx& k, int b0, int nb, hipStream_t sA, hipStream_t s
             if (k.wait_count && !k.wait_count->wait_for(i)) return PC_ERR_STATE;             // the other chain failed
             HIPCHK(hipStreamWaitEvent(sA, k.waitv[i], 0));
         }
-        PCCHK(chain_params(k, step, b0, nb, sA, sB, eA, eB, tag));
+        PCCHK(chain_params(k, step, b0, nb, sA, tag));
         const size_t so = (size_t)step * k.M * SLICE + (size_t)b0 * pi * SLICE;
         // forward path: likelihood of slice `step` of image b at lik[((b * lik_nch) + 32 * step + c) * HW + p]
         float* lik = k.lik ? k.lik + ((size_t)b0 * k.lik_nch + (size_t)32 * step) * pi : nullptr;
@@ -1381,15 +1324,6 @@ int encode_lane(const ChainCtx& k, int b0, int nb, hipStream_t sA, hipStream_t s
                               img(k.ye, b0, pi * D0) + 32 * i, D0, lik, lik_sb, sA,
                               k.cust_map ? k.cust_map + ((size_t)b0 * D0 + (size_t)SLICE * i) * pi : nullptr, (int64_t)D0 * (int64_t)pi));
         }
-        if (k.so_sym && b0 == 0 && nb == k.B) {                                          // hand this slice's symbols to the host now
-            const int i = step >= NS0 ? step - NS0 : step;
-            const size_t ns = k.M * SLICE;
-            HIPCHK(hipEventRecord(c->slice_ev[i], sA));
-            HIPCHK(hipStreamWaitEvent(c->copy_stream, c->slice_ev[i], 0));
-            HIPCHK(hipMemcpyAsync(k.so_sym + (size_t)i * ns, k.sym + so, ns * 4, hipMemcpyDeviceToHost, c->copy_stream));
-            HIPCHK(hipMemcpyAsync(k.so_idx + (size_t)i * ns, k.idx + so, ns * 4, hipMemcpyDeviceToHost, c->copy_stream));
-            HIPCHK(hipEventRecord(c->slice_ev[NS0 + i], c->copy_stream));
-        }
         PCCHK(chain_lrp(k, step, b0, nb, sA, tag));
         if (k.sig) {
             const int i = step >= NS0 ? step - NS0 : step;
@@ -1400,8 +1334,8 @@ int encode_lane(const ChainCtx& k, int b0, int nb, hipStream_t sA, hipStream_t s
     return PC_OK;
 }
 
-int decode_lane(const ChainCtx& k, int b0, int nb, hipStream_t sA, hipStream_t sB, hipEvent_t eA, hipEvent_t eB, const std::string& tag,
-                const uint8_t* const* y_strings, const size_t* y_lens, int nt)
+int decode_lane(const ChainCtx& k, int b0, int nb, hipStream_t sA, const std::string& tag, const uint8_t* const* y_strings, const size_t* y_lens,
+                int nt)
 {
     pc_codec* c = k.c;
     HIPCHK(hipSetDevice(c->device));
@@ -1416,7 +1350,7 @@ int decode_lane(const ChainCtx& k, int b0, int nb, hipStream_t sA, hipStream_t s
             if (k.wait_count && !k.wait_count->wait_for(i)) return PC_ERR_STATE;             // the other chain failed
             HIPCHK(hipStreamWaitEvent(sA, k.waitv[i], 0));
         }
-        PCCHK(chain_params(k, step, b0, nb, sA, sB, eA, eB, tag));
+        PCCHK(chain_params(k, step, b0, nb, sA, tag));
         const size_t so = (size_t)step * k.M * SLICE + (size_t)b0 * pi * SLICE;
         const bool e = step >= NS0;
         const int i = e ? step - NS0 : step;
@@ -1425,18 +1359,12 @@ int decode_lane(const ChainCtx& k, int b0, int nb, hipStream_t sA, hipStream_t s
                                 c->scale_table, c->n_table, c->scale_bound, k.idx + so, nullptr, sA,
                                 (e && k.cust_map) ? k.cust_map + ((size_t)b0 * D0 + (size_t)SLICE * i) * pi : nullptr, (int64_t)D0 * (int64_t)pi,
                                 k.idx8 + so));
-        static const bool slow_dec = pc_tune("PC_DEC_FAST", 1) == 0;   // A/B switch
         uint8_t* h_idx8 = reinterpret_cast<uint8_t*>(h_idx);
-        if (slow_dec) HIPCHK(hipMemcpyAsync(h_idx, k.idx + so, per * nb * 4, hipMemcpyDeviceToHost, sA));
-        else HIPCHK(hipMemcpyAsync(h_idx8, k.idx8 + so, per * nb, hipMemcpyDeviceToHost, sA));
+        HIPCHK(hipMemcpyAsync(h_idx8, k.idx8 + so, per * nb, hipMemcpyDeviceToHost, sA));
         HIPCHK(hipStreamSynchronize(sA));
         const auto td0 = std::chrono::steady_clock::now();
         const size_t slot = e ? (size_t)NS0 + (size_t)NS0 * k.level + i : (size_t)step;
-        if (slow_dec)
-            PCCHK(pc_rans_decode_batch(y_strings + slot * k.B + b0, y_lens + slot * k.B + b0, nb, h_idx, per, c->gc.cdf.data(), c->gc.n, c->gc.stride,
-                                       c->gc.len.data(), c->gc.off.data(), h_sym, nt));
-        else
-            PCCHK(pc::rans_decode_u8_batch(y_strings + slot * k.B + b0, y_lens + slot * k.B + b0, nb, h_idx8, per, c->gc.dec(), h_sym, nt));   // :894,969
+        PCCHK(pc::rans_decode_u8_batch(y_strings + slot * k.B + b0, y_lens + slot * k.B + b0, nb, h_idx8, per, c->gc.dec(), h_sym, nt));   // :894,969
         { std::lock_guard<std::mutex> lk(c->buf_mu); c->t_host_decode_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - td0).count(); }
         HIPCHK(hipMemcpyAsync(k.sym + so, h_sym, per * nb * 4, hipMemcpyHostToDevice, sA));
         float* dst = e ? img(k.ye, b0, pi * D0) + 32 * i : img(k.yb, b0, pi * D0) + 32 * i;
@@ -1456,14 +1384,10 @@ int decode_lane(const ChainCtx& k, int b0, int nb, hipStream_t sA, hipStream_t s
 int run_chain(const ChainCtx& k, hipStream_t st, bool decode, const uint8_t* const* y_strings, const size_t* y_lens)
 {
     pc_codec* c = k.c;
+    if (c->serial_profile() || c->opt_serial)    // sequential on the caller's stream (the profiling configuration); otherwise even one lane
+        return decode ? decode_lane(k, 0, k.B, st, "", y_strings, y_lens, c->n_threads == 1 ? 1 : 0)   // runs on lane 0's stream
+                      : encode_lane(k, 0, k.B, st, "");
     const int nl = lane_count(c, k.B, decode);
-    if (nl == 1) {   // sequential on the caller's stream (also the profiling configuration)
-        static const bool two = pc_tune("PC_DUAL_STREAM", 1) != 0;
-        if (!two || c->serial_profile() || c->opt_serial) {
-            return decode ? decode_lane(k, 0, k.B, st, st, nullptr, nullptr, "", y_strings, y_lens, c->n_threads == 1 ? 1 : 0)
-                          : encode_lane(k, 0, k.B, st, st, nullptr, nullptr, "");
-        }
-    }
     PCCHK(ensure_lanes(c, nl));
     // pre-create every lane's workspace (no allocation inside lanes / threads)
     for (int g = 0; g < nl; ++g) {
@@ -1481,16 +1405,12 @@ int run_chain(const ChainCtx& k, hipStream_t st, bool decode, const uint8_t* con
     std::vector<std::thread> threads;
     for (int g = 0; g < nl; ++g) {
         const int b0 = (int)((long)k.B * g / nl), nb = (int)((long)k.B * (g + 1) / nl) - b0;
-        pc_codec::Lane& L = c->lanes[g];
+        const hipStream_t sA = c->lanes[g].sA;
         const std::string tag = std::to_string(g);
-        if (decode) {
-            threads.emplace_back([&, g, b0, nb, tag] {
-                pc_codec::Lane& LL = c->lanes[g];
-                rcs[g] = decode_lane(k, b0, nb, LL.sA, LL.sB, LL.eA, LL.eB, tag, y_strings, y_lens, c->n_threads == 1 ? 1 : 0);
-            });
-        } else {
-            rcs[g] = encode_lane(k, b0, nb, L.sA, L.sB, L.eA, L.eB, tag);
-        }
+        if (decode)
+            threads.emplace_back([&, g, b0, nb, sA, tag] { rcs[g] = decode_lane(k, b0, nb, sA, tag, y_strings, y_lens, c->n_threads == 1 ? 1 : 0); });
+        else
+            rcs[g] = encode_lane(k, b0, nb, sA, tag);
     }
     for (auto& t : threads) t.join();                                                          // nothing between creation and join can return
     int rc = PC_OK;
@@ -1542,8 +1462,7 @@ int encode_streams(pc_codec* c, const int32_t* hs, const int32_t* hi, int first_
 // the decoder one chain's host rANS round trip hides behind the other chain's kernels -- without halving M as batch lanes do.
 bool pipeline_enabled(const pc_codec* c)
 {
-    static const bool on = pc_tune("PC_PIPELINE", 1) != 0;
-    return on && !c->serial_profile() && !c->opt_serial;
+    return !c->serial_profile() && !c->opt_serial;
 }
 
 // Second set of the level-specific buffers of a chain (decoded enhancement slices, per-slice mu / scale / symbols / indexes, mask
@@ -1576,6 +1495,101 @@ int ensure_pipeline(pc_codec* c, size_t M)
         PCCHK(c->buf(std::string(tag) + "_t0", M * 224, &dummy));
         PCCHK(c->buf(std::string(tag) + "_t1", M * 176, &dummy));
     }
+    return PC_OK;
+}
+
+// The chain's buffers, under the names the taps read (pc_codec_read_tap), and the base pass's context over them: geometry, steps
+// [0, NS0), mu_base / scale_base on set 0.  `y` is the encoders' only, `idx8` the decoder's.  compress and decompress consume the
+// custom map and the REM checkpoint given for the call; forward takes neither and leaves them for the next call.
+enum class CallKind { compress, forward, decompress };
+
+int chain_setup(pc_codec* c, CallKind kind, int B, int h, int w, ChainCtx* k)
+{
+    std::memset(k, 0, sizeof(*k));
+    const size_t M = (size_t)B * h * w;
+    if (kind != CallKind::decompress) PCCHK(c->buf("y", M * MLAT, &k->y));
+    PCCHK(c->buf("latent_means", M * MLAT, &k->lm));
+    PCCHK(c->buf("latent_scales", M * MLAT, &k->ls));
+    PCCHK(c->buf("yhat_base", M * D0, &k->yb));
+    PCCHK(c->buf("yhat_enh", M * D0, &k->ye));
+    PCCHK(c->buf("mu", M * SLICE * 2 * NS0, &k->mu));            // per-slice mu / scale kept for taps
+    PCCHK(c->buf("scale", M * SLICE * 2 * NS0, &k->scale));
+    PCCHK(c->buf("thr", (size_t)B * NS0, &k->thr));
+    PCCHK(c->buf("sym", M * SLICE * 2 * NS0, &k->sym));
+    PCCHK(c->buf("idx", M * SLICE * 2 * NS0, &k->idx));
+    if (kind == CallKind::decompress) PCCHK(c->buf("idx8", M * SLICE * 2 * NS0, &k->idx8));
+    k->c = c; k->B = B; k->h = h; k->w = w; k->HW = h * w; k->M = M;
+    k->step0 = 0; k->step1 = NS0;
+    k->mu_base = k->mu; k->scale_base = k->scale;
+    if (kind != CallKind::forward) {
+        k->cust_map = c->cust_map; c->cust_map = nullptr;
+        k->rem_ckpt = c->rem_ckpt; c->rem_ckpt = nullptr;
+    }
+    return PC_OK;
+}
+
+// the enhancement pass (steps [NS0, 2*NS0)) of one level over the buffer set of `base`
+ChainCtx level_ctx(const ChainCtx& base, int level, double quality, int mask_pol)
+{
+    ChainCtx k = base;
+    k.step0 = NS0; k.step1 = 2 * NS0; k.level = level;
+    k.mode = mask_mode_for(k.cust_map ? PC_MASK_POINT_BASED_STD : mask_pol, quality, &k.q);   // a custom map overrides the policy
+    k.quality = quality; k.mask_pol = mask_pol;
+    return k;
+}
+
+// Encoder pipeline: base slice t of `base` on `st`, enhancement slice t-1 of `enh` on pipe_stream, enqueued alternately.  after_base
+// (if set) is enqueued on `st` right behind the last base slice, before the enhancement slices still to come.  join: pipe_stream back into `st` at the end;
+// without it `st` goes on with other work beside pipe_stream and the caller joins them later.
+int encode_pipelined(const ChainCtx& base, const ChainCtx& enh, hipStream_t st, bool join, const std::function<int()>& after_base)
+{
+    pc_codec* c = base.c;
+    PCCHK(ensure_pipeline(c, base.M));
+    HIPCHK(hipEventRecord(c->pipe_ev[NS0], st));
+    HIPCHK(hipStreamWaitEvent(c->pipe_stream, c->pipe_ev[NS0], 0));
+    ChainCtx kb = base, ke = enh;
+    kb.sig = c->pipe_ev.data();
+    ke.waitv = c->pipe_ev.data();
+    for (int t = 0; t <= NS0; ++t) {
+        if (t < NS0) {
+            kb.step0 = t; kb.step1 = t + 1;
+            PCCHK(encode_lane(kb, 0, kb.B, st, "PA"));                                      // :729-767
+            if (t == NS0 - 1 && after_base) PCCHK(after_base());
+        }
+        if (t >= 1) {
+            ke.step0 = NS0 + t - 1; ke.step1 = NS0 + t;
+            PCCHK(encode_lane(ke, 0, ke.B, c->pipe_stream, "PB"));                          // :775-845
+        }
+    }
+    if (join) {
+        HIPCHK(hipEventRecord(c->pipe_ev[NS0 + 1], c->pipe_stream));
+        HIPCHK(hipStreamWaitEvent(st, c->pipe_ev[NS0 + 1], 0));
+    }
+    return PC_OK;
+}
+
+// Two decoder chains side by side: `ka` on `st` from a new host thread, `kb` on pipe_stream from this one, so that each chain's host
+// rANS round trip hides behind the other chain's kernels.  When ka publishes its slices to kb (sig_count), its failure releases kb.
+// Returns the first error, ka's before kb's.
+int decode_pair(const ChainCtx& ka, const ChainCtx& kb, hipStream_t st, const uint8_t* const* y_strings, const size_t* y_lens, int nt)
+{
+    pc_codec* c = ka.c;
+    HIPCHK(hipEventRecord(c->pipe_ev[NS0], st));
+    HIPCHK(hipStreamWaitEvent(c->pipe_stream, c->pipe_ev[NS0], 0));
+    int ra = PC_OK;
+    std::thread ta([&] {
+        ra = decode_lane(ka, 0, ka.B, st, "PA", y_strings, y_lens, nt);
+        if (ra != PC_OK && ka.sig_count) ka.sig_count->fail();                             // release the other chain
+    });
+    const int rb = decode_lane(kb, 0, kb.B, c->pipe_stream, "PB", y_strings, y_lens, nt);
+    ta.join();
+    // join pipe_stream back into `st` whatever happened: a failed call must not leave work of its own running beside the next one
+    const hipError_t ej = hipEventRecord(c->pipe_ev[NS0 + 1], c->pipe_stream);
+    const hipError_t ew = ej == hipSuccess ? hipStreamWaitEvent(st, c->pipe_ev[NS0 + 1], 0) : ej;
+    if (ra != PC_OK || rb != PC_OK) { (void)hipStreamSynchronize(c->pipe_stream); (void)hipStreamSynchronize(st); }
+    if (ra != PC_OK) return ra;
+    if (rb != PC_OK) return rb;
+    HIPCHK(ew);
     return PC_OK;
 }
 
@@ -1636,26 +1650,12 @@ int compress_impl(pc_codec* c, const float* x, int B, int H, int W, const double
     c->last_B = B; c->last_h16 = h; c->last_w16 = w;
 
     ChainCtx k;
-    std::memset(&k, 0, sizeof(k));
+    PCCHK(chain_setup(c, CallKind::compress, B, h, w, &k));
     float *z, *z_hat;
     int32_t* z_sym;
-    PCCHK(c->buf("y", M * MLAT, &k.y));
     PCCHK(c->buf("z", (size_t)B * ZHW * NCH, &z));
     PCCHK(c->buf("z_hat", (size_t)B * ZHW * NCH, &z_hat));
     PCCHK(c->buf("z_sym", (size_t)B * ZHW * NCH, &z_sym));
-    PCCHK(c->buf("latent_means", M * MLAT, &k.lm));
-    PCCHK(c->buf("latent_scales", M * MLAT, &k.ls));
-    PCCHK(c->buf("yhat_base", M * D0, &k.yb));
-    PCCHK(c->buf("yhat_enh", M * D0, &k.ye));
-    PCCHK(c->buf("mu", M * SLICE * 2 * NS0, &k.mu));            // per-slice mu / scale kept for taps
-    PCCHK(c->buf("scale", M * SLICE * 2 * NS0, &k.scale));
-    PCCHK(c->buf("thr", (size_t)B * NS0, &k.thr));
-    PCCHK(c->buf("sym", M * SLICE * 2 * NS0, &k.sym));
-    PCCHK(c->buf("idx", M * SLICE * 2 * NS0, &k.idx));
-    k.c = c; k.B = B; k.h = h; k.w = w; k.HW = HW; k.M = M;
-    k.mu_base = k.mu; k.scale_base = k.scale;
-    k.cust_map = c->cust_map; c->cust_map = nullptr;
-    k.rem_ckpt = c->rem_ckpt; c->rem_ckpt = nullptr;
 
     const size_t n_half = (size_t)NS0 * M * SLICE, n_z = (size_t)B * ZHW * NCH;      // symbols of one pass / of z
     const size_t per = (size_t)SLICE * HW, per_z = (size_t)NCH * ZHW;
@@ -1678,20 +1678,11 @@ int compress_impl(pc_codec* c, const float* x, int B, int H, int W, const double
     PCCHK(h_a(c, st, k.y, B, h, w, z));                                                  // :700
     PCCHK(pc_eb_quant_launch(z, B, ZHW, NCH, c->medians, z_sym, z_hat, st));             // :702-704
     PCCHK(hyper(c, st, z_hat, B, zh, zw, any_enh ? 1.0 : 0.0, k.lm, k.ls));              // :705-715
-    // The LAST coded level has no later GPU pass to hide its entropy coding behind: with a single encoder lane its slices are copied
-    // out one by one (side stream) and coded while the rest of the chain still runs; only the last slice's coding is exposed.
-    int last_coded = -1, first_coded = -1;
-    for (int l = 0; l < n_levels; ++l) if (!(qualities[l] <= 0)) { last_coded = l; if (first_coded < 0) first_coded = l; }
-    // Default OFF since round 3 (PC_NO_STREAMED_ENCODE=0 switches it on): the per-slice copies and events of the side stream cost the
-    // overlapped bench 3.4 % (46.7 -> 48.2 MP/s) and buy a sequential caller 0.6 ms of host coding per call -- nothing measurable
-    // (profiles/r03_t_streamed_encode_ab.log)
-    static const bool no_stream = pc_tune("PC_NO_STREAMED_ENCODE", 1) != 0;
-    const bool can_stream = !no_stream && lane_count(c, B, false) == 1;
-    if (can_stream && !c->copy_stream) {
-        HIPCHK(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
-        c->slice_ev.resize(2 * NS0);
-        for (auto& e : c->slice_ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    }
+    // Streaming the last coded level's slices out one by one (side stream) while the rest of its chain ran was removed: the per-slice
+    // copies and events cost the overlapped bench 3.4 % (46.7 -> 48.2 MP/s) and bought a sequential caller 0.6 ms of host coding per
+    // call -- nothing measurable (profiles/r03_t_streamed_encode_ab.log).
+    int first_coded = -1, n_coded_total = 0;
+    for (int l = 0; l < n_levels; ++l) if (!(qualities[l] <= 0)) { ++n_coded_total; if (first_coded < 0) first_coded = l; }
     auto base_d2h = [&]() -> int {
         HIPCHK(hipMemcpyAsync(c->h_sym, k.sym, n_half * 4, hipMemcpyDeviceToHost, st));
         HIPCHK(hipMemcpyAsync(c->h_idx, k.idx, n_half * 4, hipMemcpyDeviceToHost, st));
@@ -1704,40 +1695,16 @@ int compress_impl(pc_codec* c, const float* x, int B, int H, int W, const double
     // streams -- level j of the coded ones on pipe_stream / set 0 (j even) or on `st` / set 1 (j odd) -- so that level j+1's chain runs
     // beside level j's instead of behind it (the chains are independent; each alone leaves the MFMA pipes as idle as a sequential
     // Config-2 step does).  The host codes level j-1 while both run, as before.
-    int n_coded_total = 0;
-    for (int l = 0; l < n_levels; ++l) n_coded_total += !(qualities[l] <= 0) ? 1 : 0;
-    const bool two_levels = piped && !can_stream && n_coded_total >= 2;
+    const bool two_levels = piped && n_coded_total >= 2;
     ChainCtx k2;
     if (two_levels) PCCHK(second_level_set(c, k, false, &k2));
     if (piped) {
-        // base slice t on `st`, enhancement slice t-1 of the first coded level on pipe_stream, enqueued alternately
-        PCCHK(ensure_pipeline(c, M));
-        HIPCHK(hipEventRecord(c->pipe_ev[NS0], st));
-        HIPCHK(hipStreamWaitEvent(c->pipe_stream, c->pipe_ev[NS0], 0));
-        ChainCtx kb = k, ke = k;
-        kb.enh = false; kb.mode = 0; kb.sig = c->pipe_ev.data();
-        ke.enh = true; ke.level = first_coded; ke.waitv = c->pipe_ev.data();
-        ke.mode = mask_mode_for(k.cust_map ? PC_MASK_POINT_BASED_STD : mask_pol, qualities[first_coded], &ke.q);
-        ke.quality = qualities[first_coded]; ke.mask_pol = mask_pol;
+        // base slice t on `st`, enhancement slice t-1 of the first coded level on pipe_stream; with two levels in flight `st` goes on
+        // with the next level (pipe_stream is joined at the end)
+        ChainCtx ke = level_ctx(k, first_coded, qualities[first_coded], mask_pol);
         ke.masks = masks_out ? masks_out[first_coded] : nullptr;
-        if (can_stream && first_coded == last_coded) { ke.so_sym = c->h_sym + n_half; ke.so_idx = c->h_idx + n_half; }
-        for (int t = 0; t <= NS0; ++t) {
-            if (t < NS0) {
-                kb.step0 = t; kb.step1 = t + 1;
-                PCCHK(encode_lane(kb, 0, B, st, st, nullptr, nullptr, "PA"));                // :729-767
-                if (t == NS0 - 1) PCCHK(base_d2h());
-            }
-            if (t >= 1) {
-                ke.step0 = NS0 + t - 1; ke.step1 = NS0 + t;
-                PCCHK(encode_lane(ke, 0, B, c->pipe_stream, c->pipe_stream, nullptr, nullptr, "PB"));   // :775-845
-            }
-        }
-        if (!two_levels) {                                                                // (two levels in flight: `st` goes on with the next level; joined at the end)
-            HIPCHK(hipEventRecord(c->pipe_ev[NS0 + 1], c->pipe_stream));
-            HIPCHK(hipStreamWaitEvent(st, c->pipe_ev[NS0 + 1], 0));
-        }
+        PCCHK(encode_pipelined(k, ke, st, !two_levels, base_d2h));
     } else {
-        k.step0 = 0; k.step1 = NS0; k.enh = false; k.mode = 0;
         PCCHK(run_chain(k, st, false, nullptr, nullptr));                                // :729-767
         PCCHK(base_d2h());
     }
@@ -1766,59 +1733,21 @@ int compress_impl(pc_codec* c, const float* x, int B, int H, int W, const double
     };
     for (int l = 0; l < n_levels; ++l) {
         if (qualities[l] <= 0) continue;                                                 // base only: nothing level-specific to code
-        k.step0 = NS0; k.step1 = 2 * NS0; k.enh = true; k.level = l;
-        k.mode = mask_mode_for(k.cust_map ? PC_MASK_POINT_BASED_STD : mask_pol, qualities[l], &k.q);   // a custom map overrides the policy
-        k.quality = qualities[l]; k.mask_pol = mask_pol;
-        k.masks = masks_out ? masks_out[l] : nullptr;
+        // two levels in flight: coded level number n_coded even -> set 0 on pipe_stream (the first one is already enqueued there,
+        // pipelined with the base chain), odd -> set 1 on `st` (behind the base chain, which it needs and which ran there)
+        const bool odd = two_levels && (n_coded & 1);
+        ChainCtx kl = level_ctx(odd ? k2 : k, l, qualities[l], mask_pol);
+        kl.masks = masks_out ? masks_out[l] : nullptr;
+        const hipStream_t sx = two_levels && !odd ? c->pipe_stream : st;
+        if (!(piped && l == first_coded)) {                                              // (else already enqueued, pipelined with the base chain)
+            if (two_levels) PCCHK(encode_lane(kl, 0, B, sx, odd ? "PA" : "PB"));          // :775-845
+            else PCCHK(run_chain(kl, st, false, nullptr, nullptr));
+        }
         const int bufsel = n_coded & 1;
         const size_t off = (size_t)(1 + bufsel) * n_half;
-        const bool pre = piped && l == first_coded;                                      // already enqueued, pipelined with the base chain
-        if (can_stream && l == last_coded) {
-            if (!pre) {
-                k.so_sym = c->h_sym + off; k.so_idx = c->h_idx + off;
-                PCCHK(run_chain(k, st, false, nullptr, nullptr));                        // :775-845, slices streamed out
-                k.so_sym = k.so_idx = nullptr;
-            }
-            c->res_level_coded[l] = 1;
-            ++n_coded;
-            int r = drain(pending, pending_buf);                                         // the pass before, meanwhile
-            if (r != PC_OK) rc = r;
-            pending = -2;                                                                // nothing left to drain afterwards
-            const double te = now();
-            for (int i = 0; i < NS0; ++i) {
-                HIPCHK(hipEventSynchronize(c->slice_ev[NS0 + i]));
-                const double ts = now();
-                r = encode_streams(c, c->h_sym + off + (size_t)i * M * SLICE, c->h_idx + off + (size_t)i * M * SLICE, NS0 + NS0 * l + i, 1, B, per,
-                                   nullptr, nullptr, per_z);
-                if (r != PC_OK) rc = r;
-                if (i == NS0 - 1) t_enc_last = now() - ts;
-            }
-            t_host += now() - te;
-            continue;
-        }
-        if (two_levels) {
-            // coded level number n_coded: even -> set 0 on pipe_stream (the first one is already enqueued there, pipelined with the base
-            // chain), odd -> set 1 on `st` (behind the base chain, which it needs and which ran there)
-            const bool odd = n_coded & 1;
-            ChainCtx kl = odd ? k2 : k;
-            kl.step0 = NS0; kl.step1 = 2 * NS0; kl.enh = true; kl.level = l; kl.mode = k.mode; kl.q = k.q; kl.quality = k.quality; kl.mask_pol = k.mask_pol;
-            kl.masks = k.masks;
-            hipStream_t sx = odd ? st : c->pipe_stream;
-            if (!pre) PCCHK(encode_lane(kl, 0, B, sx, sx, nullptr, nullptr, odd ? "PA" : "PB"));   // :775-845
-            HIPCHK(hipMemcpyAsync(c->h_sym + off, kl.sym + n_half, n_half * 4, hipMemcpyDeviceToHost, sx));
-            HIPCHK(hipMemcpyAsync(c->h_idx + off, kl.idx + n_half, n_half * 4, hipMemcpyDeviceToHost, sx));
-            HIPCHK(hipEventRecord(c->lvl_events[1 + l], sx));
-            c->res_level_coded[l] = 1;
-            ++n_coded;
-            const int r = drain(pending, pending_buf);                                   // the level before last, meanwhile
-            if (r != PC_OK) rc = r;
-            pending = l; pending_buf = bufsel;
-            continue;
-        }
-        if (!pre) PCCHK(run_chain(k, st, false, nullptr, nullptr));                      // :775-845
-        HIPCHK(hipMemcpyAsync(c->h_sym + off, k.sym + n_half, n_half * 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(c->h_idx + off, k.idx + n_half, n_half * 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipEventRecord(c->lvl_events[1 + l], st));
+        HIPCHK(hipMemcpyAsync(c->h_sym + off, kl.sym + n_half, n_half * 4, hipMemcpyDeviceToHost, sx));
+        HIPCHK(hipMemcpyAsync(c->h_idx + off, kl.idx + n_half, n_half * 4, hipMemcpyDeviceToHost, sx));
+        HIPCHK(hipEventRecord(c->lvl_events[1 + l], sx));
         c->res_level_coded[l] = 1;
         ++n_coded;
         // this level is queued on the GPU: entropy-code the pass before it meanwhile (its staging buffer is the other one)
@@ -1826,10 +1755,8 @@ int compress_impl(pc_codec* c, const float* x, int B, int H, int W, const double
         if (r != PC_OK) rc = r;
         pending = l; pending_buf = bufsel;
     }
-    if (pending != -2) {
-        const int r = drain(pending, pending_buf);
-        if (r != PC_OK) rc = r;
-    }
+    const int r = drain(pending, pending_buf);
+    if (r != PC_OK) rc = r;
     if (two_levels) {                                                                    // pipe_stream back into the caller's stream
         HIPCHK(hipEventRecord(c->pipe_ev[NS0 + 1], c->pipe_stream));
         HIPCHK(hipStreamWaitEvent(st, c->pipe_ev[NS0 + 1], 0));
@@ -1919,30 +1846,17 @@ extern "C" int pc_codec_forward(pc_codec* c, const float* x, int B, int H, int W
     if (order.rc != PC_OK) return order.rc;
     g_prof = c->profile ? c : nullptr;
     g_rowtabs = c->rowtabs;
-    const int h = H / 16, w = W / 16, zh = H / 64, zw = W / 64, HW = h * w, ZHW = zh * zw;
-    const size_t M = (size_t)B * HW;
+    const int h = H / 16, w = W / 16, zh = H / 64, zw = W / 64, ZHW = zh * zw;
     const bool enh = quality != 0 || force_enhanced != 0;                                // :1063 "if quality == 0 and force_enhanced is False"
     c->last_B = B; c->last_h16 = h; c->last_w16 = w;
 
     ChainCtx k;
-    std::memset(&k, 0, sizeof(k));
+    PCCHK(chain_setup(c, CallKind::forward, B, h, w, &k));
     float *z, *z_hat;
     int32_t* z_sym;
-    PCCHK(c->buf("y", M * MLAT, &k.y));
     PCCHK(c->buf("z", (size_t)B * ZHW * NCH, &z));
     PCCHK(c->buf("z_hat", (size_t)B * ZHW * NCH, &z_hat));
     PCCHK(c->buf("z_sym", (size_t)B * ZHW * NCH, &z_sym));
-    PCCHK(c->buf("latent_means", M * MLAT, &k.lm));
-    PCCHK(c->buf("latent_scales", M * MLAT, &k.ls));
-    PCCHK(c->buf("yhat_base", M * D0, &k.yb));
-    PCCHK(c->buf("yhat_enh", M * D0, &k.ye));
-    PCCHK(c->buf("mu", M * SLICE * 2 * NS0, &k.mu));
-    PCCHK(c->buf("scale", M * SLICE * 2 * NS0, &k.scale));
-    PCCHK(c->buf("thr", (size_t)B * NS0, &k.thr));
-    PCCHK(c->buf("sym", M * SLICE * 2 * NS0, &k.sym));
-    PCCHK(c->buf("idx", M * SLICE * 2 * NS0, &k.idx));
-    k.c = c; k.B = B; k.h = h; k.w = w; k.HW = HW; k.M = M;
-    k.mu_base = k.mu; k.scale_base = k.scale;
     k.lik = y_lik; k.lik_nch = enh ? 2 * D0 : D0;
 
     PCCHK(g_a(c, st, x, B, H, W, k.y));                                                  // :1013
@@ -1950,32 +1864,13 @@ extern "C" int pc_codec_forward(pc_codec* c, const float* x, int B, int H, int W
     PCCHK(pc_eb_quant_launch(z, B, ZHW, NCH, c->medians, z_sym, z_hat, st));             // :401-403
     PCCHK(pc_eb_likelihood_launch(z_sym, B, ZHW, NCH, c->medians, c->eb_net, z_lik, st));   // :400
     PCCHK(hyper(c, st, z_hat, B, zh, zw, enh ? 1.0 : 0.0, k.lm, k.ls));                  // :404-417
+    ChainCtx ke = level_ctx(k, 0, quality, mask_pol);
+    ke.masks = masks_out;
     if (enh && pipeline_enabled(c) && lane_count(c, B, false) == 1) {
-        // base slice t || enhancement slice t-1, as in compress_impl
-        PCCHK(ensure_pipeline(c, M));
-        HIPCHK(hipEventRecord(c->pipe_ev[NS0], st));
-        HIPCHK(hipStreamWaitEvent(c->pipe_stream, c->pipe_ev[NS0], 0));
-        ChainCtx kb = k, ke = k;
-        kb.enh = false; kb.mode = 0; kb.sig = c->pipe_ev.data();
-        ke.enh = true; ke.level = 0; ke.waitv = c->pipe_ev.data(); ke.masks = masks_out;
-        ke.mode = mask_mode_for(mask_pol, quality, &ke.q);
-        ke.quality = quality; ke.mask_pol = mask_pol;
-        for (int t = 0; t <= NS0; ++t) {
-            if (t < NS0) { kb.step0 = t; kb.step1 = t + 1; PCCHK(encode_lane(kb, 0, B, st, st, nullptr, nullptr, "PA")); }                       // :1033-1061
-            if (t >= 1) { ke.step0 = NS0 + t - 1; ke.step1 = NS0 + t; PCCHK(encode_lane(ke, 0, B, c->pipe_stream, c->pipe_stream, nullptr, nullptr, "PB")); }   // :1089-1160
-        }
-        HIPCHK(hipEventRecord(c->pipe_ev[NS0 + 1], c->pipe_stream));
-        HIPCHK(hipStreamWaitEvent(st, c->pipe_ev[NS0 + 1], 0));
+        PCCHK(encode_pipelined(k, ke, st, true, nullptr));                               // :1033-1061 || :1089-1160
     } else {
-        k.step0 = 0; k.step1 = NS0; k.enh = false; k.mode = 0;
         PCCHK(run_chain(k, st, false, nullptr, nullptr));                                // :1033-1061
-        if (enh) {
-            k.step0 = NS0; k.step1 = 2 * NS0; k.enh = true; k.level = 0;
-            k.mode = mask_mode_for(mask_pol, quality, &k.q);
-            k.quality = quality; k.mask_pol = mask_pol;
-            k.masks = masks_out;
-            PCCHK(run_chain(k, st, false, nullptr, nullptr));                            // :1089-1160
-        }
+        if (enh) PCCHK(run_chain(ke, st, false, nullptr, nullptr));                      // :1089-1160
     }
     PCCHK(g_s(c, st, c->gs[enh ? 1 : 0], enh ? k.ye : k.yb, B, h, w, x_hat));            // :1065 / :1166-1170
     return PC_OK;
@@ -2008,25 +1903,11 @@ int decompress_impl(pc_codec* c, const uint8_t* const* y_strings, const size_t* 
     c->last_B = B; c->last_h16 = h; c->last_w16 = w;
 
     ChainCtx k;
-    std::memset(&k, 0, sizeof(k));
+    PCCHK(chain_setup(c, CallKind::decompress, B, h, w, &k));
     float* z_hat;
     int32_t* z_sym;
     PCCHK(c->buf("z_hat", (size_t)B * ZHW * NCH, &z_hat));
     PCCHK(c->buf("z_sym", (size_t)B * ZHW * NCH, &z_sym));
-    PCCHK(c->buf("latent_means", M * MLAT, &k.lm));
-    PCCHK(c->buf("latent_scales", M * MLAT, &k.ls));
-    PCCHK(c->buf("yhat_base", M * D0, &k.yb));
-    PCCHK(c->buf("yhat_enh", M * D0, &k.ye));
-    PCCHK(c->buf("mu", M * SLICE * 2 * NS0, &k.mu));
-    PCCHK(c->buf("scale", M * SLICE * 2 * NS0, &k.scale));
-    PCCHK(c->buf("thr", (size_t)B * NS0, &k.thr));
-    PCCHK(c->buf("sym", M * SLICE * 2 * NS0, &k.sym));
-    PCCHK(c->buf("idx", M * SLICE * 2 * NS0, &k.idx));
-    PCCHK(c->buf("idx8", M * SLICE * 2 * NS0, &k.idx8));
-    k.c = c; k.B = B; k.h = h; k.w = w; k.HW = HW; k.M = M;
-    k.mu_base = k.mu; k.scale_base = k.scale;
-    k.cust_map = c->cust_map; c->cust_map = nullptr;
-    k.rem_ckpt = c->rem_ckpt; c->rem_ckpt = nullptr;
     const size_t per = (size_t)SLICE * HW, per_z = (size_t)NCH * ZHW;
     // decompress() returns with work still in flight -- x_hat, and the chains' LAST host-to-device symbol copies, which read the pinned
     // staging asynchronously.  The host is about to write that staging again (the z symbols below, then every slice's) and may re-allocate it:
@@ -2053,38 +1934,19 @@ int decompress_impl(pc_codec* c, const uint8_t* const* y_strings, const size_t* 
     c->t_host_decode_ms = 0.0;
     int first_enh = -1;
     for (int l = 0; l < n_levels && first_enh < 0; ++l) if (qualities[l] != 0) first_enh = l;
-    static const bool pipe_dec = pc_tune("PC_PIPELINE_DEC", 1) != 0;
-    const bool piped = pipeline_enabled(c) && pipe_dec && first_enh >= 0;
+    const bool piped = pipeline_enabled(c) && first_enh >= 0;
     if (piped) {
         // base chain on `st` (own host thread) || enhancement chain of the first coded level on pipe_stream (this thread), one slice
         // apart: each chain's host rANS round trip hides behind the other chain's kernels, at full M
         PCCHK(ensure_pipeline(c, M));
         PCCHK(ensure_host_staging(c, std::max(2 * per * B, per_z * B)));
-        HIPCHK(hipEventRecord(c->pipe_ev[NS0], st));
-        HIPCHK(hipStreamWaitEvent(c->pipe_stream, c->pipe_ev[NS0], 0));
         SliceSignal recorded;
-        ChainCtx kb = k, ke = k;
-        kb.step0 = 0; kb.step1 = NS0; kb.enh = false; kb.mode = 0; kb.sig = c->pipe_ev.data(); kb.sig_count = &recorded; kb.h_off = 0;
-        ke.step0 = NS0; ke.step1 = 2 * NS0; ke.enh = true; ke.level = first_enh; ke.waitv = c->pipe_ev.data(); ke.wait_count = &recorded;
-        ke.h_off = per * B;
-        ke.mode = mask_mode_for(k.cust_map ? PC_MASK_POINT_BASED_STD : mask_pol, qualities[first_enh], &ke.q);
-        ke.quality = qualities[first_enh]; ke.mask_pol = mask_pol;
-        int rb = PC_OK;
-        std::thread tb([&] {
-            rb = decode_lane(kb, 0, B, st, st, nullptr, nullptr, "PA", y_strings, y_lens, nt);                  // :874-904
-            if (rb != PC_OK) recorded.fail();                                                                  // release the other chain
-        });
-        const int re = decode_lane(ke, 0, B, c->pipe_stream, c->pipe_stream, nullptr, nullptr, "PB", y_strings, y_lens, nt);   // :930-983
-        tb.join();
-        // join pipe_stream back into `st` whatever happened: a failed call must not leave work of its own running beside the next one
-        const hipError_t ej = hipEventRecord(c->pipe_ev[NS0 + 1], c->pipe_stream);
-        const hipError_t ew = ej == hipSuccess ? hipStreamWaitEvent(st, c->pipe_ev[NS0 + 1], 0) : ej;
-        if (rb != PC_OK || re != PC_OK) { (void)hipStreamSynchronize(c->pipe_stream); (void)hipStreamSynchronize(st); }
-        if (rb != PC_OK) return rb;
-        if (re != PC_OK) return re;
-        HIPCHK(ew);
+        ChainCtx kb = k;
+        kb.sig = c->pipe_ev.data(); kb.sig_count = &recorded;
+        ChainCtx ke = level_ctx(k, first_enh, qualities[first_enh], mask_pol);
+        ke.waitv = c->pipe_ev.data(); ke.wait_count = &recorded; ke.h_off = per * B;
+        PCCHK(decode_pair(kb, ke, st, y_strings, y_lens, nt));                           // :874-904 || :930-983
     } else {
-        k.step0 = 0; k.step1 = NS0; k.enh = false; k.mode = 0;
         PCCHK(run_chain(k, st, true, y_strings, y_lens));                                // :874-904
     }
     staging_mark.mark();
@@ -2100,32 +1962,15 @@ int decompress_impl(pc_codec* c, const uint8_t* const* y_strings, const size_t* 
         PCCHK(second_level_set(c, k, true, &k2));
         for (int l = 0; l < n_levels; ++l) if (qualities[l] == 0) PCCHK(g_s(c, st, c->gs[0], k.yb, B, h, w, x_hat + (size_t)l * img_elems));   // :907-916
         PCCHK(g_s(c, st, c->gs[1], k.ye, B, h, w, x_hat + (size_t)first_enh * img_elems));                                               // :986-990
-        auto level_ctx = [&](const ChainCtx& base, int l, size_t h_off) {
-            ChainCtx q = base;
-            q.step0 = NS0; q.step1 = 2 * NS0; q.enh = true; q.level = l; q.waitv = nullptr; q.wait_count = nullptr; q.sig = nullptr; q.sig_count = nullptr;
-            q.mode = mask_mode_for(k.cust_map ? PC_MASK_POINT_BASED_STD : mask_pol, qualities[l], &q.q);
-            q.quality = qualities[l]; q.mask_pol = mask_pol; q.h_off = h_off;
-            return q;
-        };
         for (size_t p = 0; p < rest.size(); p += 2) {
             const int la = rest[p], lb = p + 1 < rest.size() ? rest[p + 1] : -1;
-            const ChainCtx ka = level_ctx(k2, la, 0);
-            int ra = PC_OK, rb = PC_OK;
+            const ChainCtx ka = level_ctx(k2, la, qualities[la], mask_pol);
             if (lb >= 0) {
-                const ChainCtx kb2 = level_ctx(k, lb, per * B);
-                HIPCHK(hipEventRecord(c->pipe_ev[NS0], st));                             // set 0 is free once the g_s that read it has run
-                HIPCHK(hipStreamWaitEvent(c->pipe_stream, c->pipe_ev[NS0], 0));
-                std::thread ta([&] { ra = decode_lane(ka, 0, B, st, st, nullptr, nullptr, "PA", y_strings, y_lens, nt); });
-                rb = decode_lane(kb2, 0, B, c->pipe_stream, c->pipe_stream, nullptr, nullptr, "PB", y_strings, y_lens, nt);
-                ta.join();
-                const hipError_t ej = hipEventRecord(c->pipe_ev[NS0 + 1], c->pipe_stream);
-                const hipError_t ew = ej == hipSuccess ? hipStreamWaitEvent(st, c->pipe_ev[NS0 + 1], 0) : ej;
-                if (ra != PC_OK || rb != PC_OK) { (void)hipStreamSynchronize(c->pipe_stream); (void)hipStreamSynchronize(st); }
-                if (ra != PC_OK) return ra;
-                if (rb != PC_OK) return rb;
-                HIPCHK(ew);
+                ChainCtx kb = level_ctx(k, lb, qualities[lb], mask_pol);
+                kb.h_off = per * B;
+                PCCHK(decode_pair(ka, kb, st, y_strings, y_lens, nt));                  // (set 0 is free once the g_s that read it has run)
             } else {
-                PCCHK(decode_lane(ka, 0, B, st, st, nullptr, nullptr, "PA", y_strings, y_lens, nt));
+                PCCHK(decode_lane(ka, 0, B, st, "PA", y_strings, y_lens, nt));
             }
             staging_mark.mark();
             PCCHK(g_s(c, st, c->gs[1], ka.ye, B, h, w, x_hat + (size_t)la * img_elems));
@@ -2139,10 +1984,7 @@ int decompress_impl(pc_codec* c, const uint8_t* const* y_strings, const size_t* 
             continue;
         }
         if (!(piped && l == first_enh)) {
-            k.step0 = NS0; k.step1 = 2 * NS0; k.enh = true; k.level = l;
-            k.mode = mask_mode_for(k.cust_map ? PC_MASK_POINT_BASED_STD : mask_pol, qualities[l], &k.q);
-            k.quality = qualities[l]; k.mask_pol = mask_pol;
-            PCCHK(run_chain(k, st, true, y_strings, y_lens));                            // :930-983
+            PCCHK(run_chain(level_ctx(k, l, qualities[l], mask_pol), st, true, y_strings, y_lens));   // :930-983
             staging_mark.mark();
         }
         PCCHK(g_s(c, st, c->gs[1], k.ye, B, h, w, out));                                 // :986-990

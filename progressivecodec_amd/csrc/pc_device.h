@@ -7,9 +7,9 @@
 
 #include "../../include/pcodec.h"
 
-// Tuning scaffolding.  The A/B builds of the profiling rounds (`make tuning` -> libpcodec_tuning.so, -DPC_TUNING; tools/env_matrix.sh,
-// tools/gpu_ab.sh select it with PC_LIB) read their switches from the environment; the PRODUCT library reads none of them -- pc_tune()
-// is the compiled-in default there.  What the product does read: PC_HOST_THREADS / PC_HOST_NO_PIN (host entropy-coding pool),
+// Tuning scaffolding of the conv kernel (pc_conv.hip: PC_CONV_* tiles, policy, debug bits).  The tuning build (`make tuning` ->
+// libpcodec_tuning.so, -DPC_TUNING; tools/env_matrix.sh, tools/gpu_ab.sh, tools/conv_tune.py select it with PC_LIB) reads them from the
+// environment; the PRODUCT library reads none of them -- pc_tune() is the compiled-in default there.  What the product does read: PC_HOST_THREADS / PC_HOST_NO_PIN (host entropy-coding pool),
 // LOCAL_RANK / LOCAL_WORLD_SIZE (the launcher's), PC_TIMING, PC_PROFILE_CSV (diagnostics); the schedule is set per object with
 // pc_codec_set_option (include/pcodec.h).
 #ifdef PC_TUNING
