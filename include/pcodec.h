@@ -219,6 +219,18 @@ PC_API int pc_codec_set_rem(pc_codec* c, const double* check_levels, int n_level
  * [B][320][H/16][W/16] that replaces the decoded base slices as the x_base input of the LatentRateReduction nets in the NEXT compress /
  * decompress call, then the pointer is cleared (what the escalation mode chains from check level to check level, :335-373).  NULL clears. */
 PC_API int pc_codec_set_rem_checkpoint(pc_codec* c, const float* checkpoint_rep);
+/* ChannelProgresssiveWACNN(u_net_post = mode) (models/CHProg_cnn.py:87-88, 277-284): the UNet post-filter (layers/unet.py) behind the
+ * synthesis transform.  mode 1: refine = Sequential(UNet(3, 16), conv3x3(16, 3)), tensors "refine.0.<unet>..." and "refine.1.{weight,bias}";
+ * mode 2: two such nets "refine.<i>.0..." / "refine.<i>.1...", of which the decode paths use refine[1] (refine[0] serves only the training
+ * forward, out of scope; its weights are loaded all the same).  Call before pc_codec_finalize, which then fails (PC_ERR_MISSING) if a
+ * refine tensor is absent; 0 (the default) is no filter.  Every decode path (decompress, _levels, _packed, forward) then returns
+ * clamp01(refine(clamp01(g_s(y_hat)))) on the padded image -- except under REM (pc_codec_set_rem n > 0), whose reference calls g_s
+ * directly (models/CHProgREM.py:977,1123).  Encoder output does not change. */
+PC_API int pc_codec_set_post_filter(pc_codec* c, int mode);
+/* refine(x) (mode 1, which 0) or refine[which](x) (mode 2), unclamped: x and out device NCHW float [B][3][H][W], out may be x.  H and W
+ * must be multiples of 4 (PC_ERR_ARG otherwise, where the reference fails in torch.cat); PC_ERR_STATE without a filter.  Scratch: 864
+ * bytes per pixel of the batch, kept by the object (section 6 of DESIGN.md). */
+PC_API int pc_codec_post_filter(pc_codec* c, int which, const float* x, int B, int H, int W, float* out, void* stream);
 PC_API int pc_codec_num_slices(const pc_codec* c);
 /* string of y slice `slice` (0..n_slices-1) or of z (slice = -1) for image b */
 PC_API int pc_codec_get_string(const pc_codec* c, int slice, int b, const uint8_t** data, size_t* len);

@@ -36,6 +36,7 @@ class CodecConfig:
     scales_min: float = 0.11
     scales_max: float = 256.0
     scales_levels: int = 64
+    u_net_post: int = 0          # CHProg_cnn.py:87-88,277-284: 0 none, 1 refine, 2 two refine nets (decoding uses refine[1])
 
     @property
     def ns0(self):
@@ -53,6 +54,8 @@ class CodecConfig:
               and self.support_progressive_slices == 5 and self.max_support_slices == 5
               and self.dim_chunk == 32 and tuple(self.division_dimension) == (320, 640)
               and self.N == 192 and self.M == 640)
+        if self.u_net_post not in (0, 1, 2):
+            raise AssertionError("u_net_post must be 0, 1 or 2 (CHProg_cnn.py:88); got %r" % (self.u_net_post,))
         if not ok:
             raise NotImplementedError(
                 "progressivecodec_amd implements the canonical ProgressiveCodec configuration only "
@@ -192,7 +195,46 @@ def param_spec(cfg: CodecConfig = CodecConfig()) -> "OrderedDict[str, tuple]":
     for fam in ("cc_mean_transforms_prog", "cc_scale_transforms_prog", "lrp_transforms_prog"):
         for i in range(cfg.ns0):
             _stack5(s, f"{fam}.{i}", cc_in_channels(cfg, fam, i))
+    # the post-filter, registered last (CHProg_cnn.py:277-284)
+    if cfg.u_net_post == 1:
+        _refine(s, "refine")
+    elif cfg.u_net_post == 2:
+        for i in range(2):
+            _refine(s, f"refine.{i}")
     return s
+
+
+# ----------------------------------------------------------------------------- UNet post-filter (layers/unet.py)
+def _uconv(spec, p, cin, cout, k):
+    spec[p + ".weight"] = ((cout, cin, k, k), "float32", "unet_conv_w")
+    spec[p + ".bias"] = ((cout,), "float32", "unet_conv_b")
+
+
+def _cbr(spec, p, cin, cout):  # ConvBlockResidual (unet.py:55-70) with SELayer(cout, reduction 16) (:37-52)
+    _uconv(spec, p + ".conv.0", cin, cout, 3)
+    _uconv(spec, p + ".conv.2", cout, cout, 3)
+    spec[p + ".conv.3.fc.0.weight"] = ((cout // 16, cout), "float32", "unet_linear_w")
+    spec[p + ".conv.3.fc.2.weight"] = ((cout, cout // 16), "float32", "unet_linear_w")
+    _uconv(spec, p + ".up_dim", cin, cout, 1)
+
+
+#: (name, in, out) of the five ConvBlockResiduals of UNet(3, 16) (unet.py:77-91)
+UNET_BLOCKS = (("conv1", 3, 32), ("conv2", 32, 64), ("conv3", 64, 128), ("up_conv3", 128, 64), ("up_conv2", 64, 16))
+
+
+def _refine(spec, p):
+    """Sequential(UNet(3, 16), conv3x3(16, 3)) (CHProg_cnn.py:278-284), in the reference's registration order."""
+    u = p + ".0"
+    for name, ci, co in UNET_BLOCKS[:3]:
+        _cbr(spec, f"{u}.{name}", ci, co)
+    for i in range(4):  # ResBlock(128, 0) (unet.py:12-34)
+        _uconv(spec, f"{u}.context_refine.{i}.conv1", 128, 128, 3)
+        _uconv(spec, f"{u}.context_refine.{i}.conv2", 128, 128, 3)
+    _uconv(spec, u + ".up3.0", 128, 256, 1)
+    _cbr(spec, u + ".up_conv3", 128, 64)
+    _uconv(spec, u + ".up2.0", 64, 128, 1)
+    _cbr(spec, u + ".up_conv2", 64, 16)
+    _uconv(spec, p + ".1", 16, 3, 3)
 
 
 # ----------------------------------------------------------------------------- REM (rate-enhancement module, SURVEY.md section 8f rank 3)

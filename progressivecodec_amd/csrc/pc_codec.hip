@@ -57,7 +57,11 @@ struct Stack5W { ConvW c[5]; };
 struct RbW { ConvW c1, c2, skip; bool has_skip = false; };                        // ResidualBlock (models/utils.py:59-87)
 struct LrrW { RbW ent_base[3], ent_enh[3], base_rep[3], enc[4]; int n_sub = 0, n_enc = 0; };   // LatentRateReduction (CHProgREM.py:12-72)
 struct HsW { ConvW c0, c2, c4, c6, c8; };
-struct GsW { WamW w0, w5; ConvW d1, d3, d6, d8; GdnW g2, g4, g7; };   // d8: the 192 -> 3 deconv in sub-pixel form (load_deconv3_subpixel)
+struct GsW { WamW w0, w5; ConvW d1, d3, d6, d8; GdnW g2, g4, g7; };
+// UNet post-filter (layers/unet.py:46-110; CHProg_cnn.py:277-284): ConvBlockResidual = conv3x3, LeakyReLU, conv3x3, SELayer (fc1 [C/16][C],
+// fc2 [C][C/16], nn.Linear layout, device) beside the 1x1 up_dim
+struct CbrW { ConvW c0, c2, up; float* fc1 = nullptr; float* fc2 = nullptr; int cout = 0; };
+struct UnetW { CbrW b1, b2, b3, u3, u2; ConvW rb1[4], rb2[4], up3, up2, out; };   // out: the trailing conv3x3(16, 3)   // d8: the 192 -> 3 deconv in sub-pixel form (load_deconv3_subpixel)
 
 struct Tables {
     std::vector<int32_t> cdf, len, off;
@@ -92,6 +96,8 @@ struct pc_codec {
     double rem_check[3] = {0, 0, 0};
     bool multi_enc = false;                      // two 3 -> 320 encoders, y = cat(g_a[0](x), g_a[1](x))  (:691-697)
     GsW gs[2];
+    int post_mode = 0;                           // u_net_post (pc_codec_set_post_filter): 0 none, 1 refine, 2 refine[0..1] (decode uses refine[1])
+    UnetW unet[2];                               // [0] refine (mode 1) / refine[0] (mode 2), [1] refine[1] (mode 2)
     ConvW ha[5];
     HsW hms[2], hss[2];
     Stack5W cc_mean[NS0], cc_scale[NS0], lrp[NS0], cc_mean_p[NS0], cc_scale_p[NS0], lrp_p[NS0];
@@ -340,6 +346,45 @@ int load_rb(pc_codec* c, const std::string& p, int ci, int co, RbW* r)
     return PC_OK;
 }
 
+int load_fc(pc_codec* c, const std::string& k, int out, int in, float** dev)     // nn.Linear(bias=False) weight [out][in], stored as is
+{
+    const HostTensor* t = find(c, k, PC_F32, {out, in});
+    if (!t) { std::fprintf(stderr, "[pcodec] missing/mis-shaped tensor %s\n", k.c_str()); return PC_ERR_MISSING; }
+    std::vector<float> v(reinterpret_cast<const float*>(t->data.data()), reinterpret_cast<const float*>(t->data.data()) + (size_t)out * in);
+    return upload(c, v, dev);
+}
+
+int load_cbr(pc_codec* c, const std::string& p, int ci, int co, CbrW* b)       // ConvBlockResidual (unet.py:55-70)
+{
+    PCCHK(load_conv(c, p + ".conv.0", ci, co, 3, 0, &b->c0));
+    PCCHK(load_conv(c, p + ".conv.2", co, co, 3, 0, &b->c2));
+    PCCHK(load_fc(c, p + ".conv.3.fc.0.weight", co / 16, co, &b->fc1));
+    PCCHK(load_fc(c, p + ".conv.3.fc.2.weight", co, co / 16, &b->fc2));
+    PCCHK(load_conv(c, p + ".up_dim", ci, co, 1, 0, &b->up));
+    b->cout = co;
+    return PC_OK;
+}
+
+// Sequential(UNet(3, 16), conv3x3(16, 3)) under prefix p (CHProg_cnn.py:277-284)
+int load_unet(pc_codec* c, const std::string& p, UnetW* u)
+{
+    const std::string n = p + ".0.";
+    PCCHK(load_cbr(c, n + "conv1", 3, 32, &u->b1));
+    PCCHK(load_cbr(c, n + "conv2", 32, 64, &u->b2));
+    PCCHK(load_cbr(c, n + "conv3", 64, 128, &u->b3));
+    for (int i = 0; i < 4; ++i) {
+        const std::string r = n + "context_refine." + std::to_string(i);
+        PCCHK(load_conv(c, r + ".conv1", 128, 128, 3, 0, &u->rb1[i]));
+        PCCHK(load_conv(c, r + ".conv2", 128, 128, 3, 0, &u->rb2[i]));
+    }
+    PCCHK(load_conv(c, n + "up3.0", 128, 256, 1, 0, &u->up3));
+    PCCHK(load_cbr(c, n + "up_conv3", 128, 64, &u->u3));
+    PCCHK(load_conv(c, n + "up2.0", 64, 128, 1, 0, &u->up2));
+    PCCHK(load_cbr(c, n + "up_conv2", 64, 16, &u->u2));
+    PCCHK(load_conv(c, p + ".1", 16, 3, 3, 0, &u->out));
+    return PC_OK;
+}
+
 int load_stack5(pc_codec* c, const std::string& p, int Cin, Stack5W* s)
 {
     int ci = Cin;
@@ -394,7 +439,7 @@ struct Group1 { const ConvW* w; const float* seg0; float* out; };   // second GE
 
 int conv(hipStream_t st, const ConvW& w, std::initializer_list<Seg> segs, int B, int H, int W, int stride,
          float* out, int ldo, int epi, const float* aux0 = nullptr, int ld0 = 0, const float* aux1 = nullptr, int ld1 = 0,
-         bool pixel_shuffle = false, const Group1* g1 = nullptr)
+         bool pixel_shuffle = false, const Group1* g1 = nullptr, float* out_relu = nullptr)
 {
     pc_conv_params q;
     std::memset(&q, 0, sizeof(q));
@@ -408,7 +453,7 @@ int conv(hipStream_t st, const ConvW& w, std::initializer_list<Seg> segs, int B,
     q.Cin = cin; q.B = B; q.H = H; q.W = W;
     q.w = w.w; q.wlayout = w.layout; q.bias = w.b; q.Cout = w.Cout;
     q.epi = epi; q.aux0 = aux0; q.ld0 = ld0; q.aux1 = aux1; q.ld1 = ld1;
-    q.out = out;
+    q.out = out; q.out_relu = out_relu;
     if (w.kind == 0) {
         fill_conv_taps(q, w.k, stride);
         q.Ho = (H + 2 * (w.k / 2) - w.k) / stride + 1;
@@ -613,6 +658,119 @@ int g_s(pc_codec* c, hipStream_t st, const GsW& g, const float* yhat, int B, int
         PCCHK(launch_conv(q, st));
     }
     return PC_OK;
+}
+
+// ------------------------------------------------------------------------------------------ UNet post-filter (layers/unet.py)
+// Scratch: named buffers of the object, used by one filter pass at a time -- every pass runs on the caller's stream `st` behind the
+// synthesis transform, after the decoder chains (decode_pair's two included) have joined it, so no two passes are ever in flight.
+// Per pixel of the padded image: 112 floats at full resolution (three 32-channel tensors and one 16-channel one), 4 x 64 at half and
+// 5 x 128 at quarter resolution = 216 floats, 864 bytes (1.8 GB for 32 x 256^2, 7.2 GB for a 3840x2160 frame).
+struct UnetScratch { float *f[4], *h[4], *q[5], *part, *s; };
+
+int unet_scratch(pc_codec* c, int B, int H, int W, UnetScratch* t)
+{
+    const size_t P = (size_t)B * H * W, Ph = P / 4, Pq = P / 16;
+    const size_t nchunk = ((size_t)H * W + PC_SE_CHUNK - 1) / PC_SE_CHUNK;          // the full-resolution squeeze has the most chunks
+    float* base;
+    const size_t total = 3 * 32 * P + 16 * P + 4 * 64 * Ph + 5 * 128 * Pq;
+    PCCHK(c->buf("pf_act", total, &base));
+    for (int i = 0; i < 3; ++i) { t->f[i] = base; base += 32 * P; }
+    t->f[3] = base; base += 16 * P;
+    for (int i = 0; i < 4; ++i) { t->h[i] = base; base += 64 * Ph; }
+    for (int i = 0; i < 5; ++i) { t->q[i] = base; base += 128 * Pq; }
+    PCCHK(c->buf("pf_part", (size_t)B * nchunk * 128, &t->part));
+    PCCHK(c->buf("pf_s", (size_t)B * 128, &t->s));
+    return PC_OK;
+}
+
+// ConvBlockResidual (unet.py:55-70): out = up_dim(x) + SE(conv3x3(leaky(conv3x3(x)))); x = `in` (a virtual concatenation), ta / tb scratch
+int cbr(hipStream_t st, const CbrW& w, std::initializer_list<Seg> in, int B, int H, int W, float* ta, float* tb, float* out,
+        const UnetScratch& t, float* out_relu = nullptr)
+{
+    const int C = w.cout;
+    PCCHK(conv(st, w.c0, in, B, H, W, 1, ta, C, PC_EPI_LEAKY));
+    PCCHK(conv(st, w.c2, {{ta, C, C}}, B, H, W, 1, tb, C, PC_EPI_NONE));
+    PCCHK(pc_se_squeeze_launch(tb, B, H * W, C, w.fc1, w.fc2, t.part, t.s, st));
+    return conv(st, w.up, in, B, H, W, 1, out, C, PC_EPI_SE_ADD, tb, C, t.s, C, false, nullptr, out_relu);
+}
+
+// the first block reads the 3-channel NCHW image through the element-gather (smallc) path
+int conv_nchw3(hipStream_t st, const ConvW& w, const float* x, int B, int H, int W, float* out, int epi, const float* aux0, const float* aux1)
+{
+    pc_conv_params q;
+    std::memset(&q, 0, sizeof(q));
+    q.nseg = 1; q.seg[0].ptr = x; q.seg[0].ld = 0; q.seg[0].nch = 3; q.Cin = 3; q.smallc = 1;
+    q.in_sb = (int64_t)3 * H * W; q.in_sc = (int64_t)H * W; q.in_sy = W; q.in_sx = 1;
+    q.B = B; q.H = H; q.W = W;
+    fill_conv_taps(q, w.k, 1);
+    q.w = w.w; q.wlayout = w.layout; q.bias = w.b; q.Cout = w.Cout;
+    q.Ho = H; q.Wo = W; q.outH = H; q.outW = W; q.M = B * H * W;
+    q.out = out; q.out_sc = 1; q.out_sx = w.Cout; q.out_sy = (int64_t)W * w.Cout; q.out_sb = (int64_t)H * W * w.Cout;
+    q.epi = epi; q.aux0 = aux0; q.ld0 = w.Cout; q.aux1 = aux1; q.ld1 = w.Cout;
+    return launch_conv(q, st);
+}
+
+// refine(x) (unet.py:93-110, then conv3x3(16, 3)): x, out NCHW [B][3][H][W], H and W multiples of 4; out may be x.  epi: PC_EPI_CLAMP01
+// on the decode paths (CHProg_cnn.py:909-914, 990-995), PC_EPI_NONE for the stand-alone call
+int unet(pc_codec* c, hipStream_t st, const UnetW& u, const float* x, int B, int H, int W, float* out, int epi)
+{
+    UnetScratch t;
+    PCCHK(unet_scratch(c, B, H, W, &t));
+    const int H2 = H / 2, W2 = W / 2, H4 = H / 4, W4 = W / 4;
+    {   // conv1 (3 -> 32, full resolution): x1 = f[0]
+        const CbrW& w = u.b1;
+        PCCHK(conv_nchw3(st, w.c0, x, B, H, W, t.f[1], PC_EPI_LEAKY, nullptr, nullptr));
+        PCCHK(conv(st, w.c2, {{t.f[1], 32, 32}}, B, H, W, 1, t.f[2], 32, PC_EPI_NONE));
+        PCCHK(pc_se_squeeze_launch(t.f[2], B, H * W, 32, w.fc1, w.fc2, t.part, t.s, st));
+        PCCHK(conv_nchw3(st, w.up, x, B, H, W, t.f[0], PC_EPI_SE_ADD, t.f[2], t.s));
+    }
+    PCCHK(pc_maxpool2_launch(t.f[0], B, H, W, 32, t.h[0], st));
+    PCCHK(cbr(st, u.b2, {{t.h[0], 32, 32}}, B, H2, W2, t.h[1], t.h[2], t.h[3], t));                      // x2 = h[3]
+    PCCHK(pc_maxpool2_launch(t.h[3], B, H2, W2, 64, t.q[0], st));
+    // conv3 (64 -> 128) with the first ResBlock's leading ReLU stored beside it: x3 = q[3], relu(x3) = q[4]
+    PCCHK(cbr(st, u.b3, {{t.q[0], 64, 64}}, B, H4, W4, t.q[1], t.q[2], t.q[3], t, t.q[4]));
+    float *xr = t.q[3], *xn = t.q[2];
+    for (int i = 0; i < 4; ++i) {   // context_refine: ResBlock(128, slope 0) = x + conv2(relu(conv1(relu(x))))  (unet.py:28-34)
+        PCCHK(conv(st, u.rb1[i], {{t.q[4], 128, 128}}, B, H4, W4, 1, t.q[1], 128, PC_EPI_RELU));
+        PCCHK(conv(st, u.rb2[i], {{t.q[1], 128, 128}}, B, H4, W4, 1, xn, 128, PC_EPI_RES, xr, 128, nullptr, 0, false, nullptr,
+                   i < 3 ? t.q[4] : nullptr));
+        std::swap(xr, xn);
+    }
+    // up3 = 1x1 128 -> 256 + PixelShuffle(2) -> d3 = h[1]; up_conv3 over cat(x2, d3)
+    PCCHK(conv(st, u.up3, {{xr, 128, 128}}, B, H4, W4, 1, t.h[1], 64, PC_EPI_NONE, nullptr, 0, nullptr, 0, true));
+    PCCHK(cbr(st, u.u3, {{t.h[3], 64, 64}, {t.h[1], 64, 64}}, B, H2, W2, t.h[2], t.h[0], t.h[2], t));
+    // up2 -> d2 = f[1]; up_conv2 over cat(x1, d2) -> f[2]
+    PCCHK(conv(st, u.up2, {{t.h[2], 64, 64}}, B, H2, W2, 1, t.f[1], 32, PC_EPI_NONE, nullptr, 0, nullptr, 0, true));
+    PCCHK(cbr(st, u.u2, {{t.f[0], 32, 32}, {t.f[1], 32, 32}}, B, H, W, t.f[2], t.f[3], t.f[2], t));
+    {   // conv3x3(16, 3) -> NCHW
+        pc_conv_params q;
+        std::memset(&q, 0, sizeof(q));
+        q.nseg = 1; q.seg[0].ptr = t.f[2]; q.seg[0].ld = 16; q.seg[0].nch = 16; q.Cin = 16;
+        q.B = B; q.H = H; q.W = W;
+        fill_conv_taps(q, 3, 1);
+        q.w = u.out.w; q.wlayout = u.out.layout; q.bias = u.out.b; q.Cout = 3;
+        q.Ho = H; q.Wo = W; q.outH = H; q.outW = W; q.M = B * H * W;
+        q.out = out; q.out_sx = 1; q.out_sy = W; q.out_sc = (int64_t)H * W; q.out_sb = 3 * q.out_sc;
+        q.epi = epi;
+        PCCHK(launch_conv(q, st));
+    }
+    return PC_OK;
+}
+
+// the filter the decode paths apply after g_s (refine for u_net_post = 1, refine[1] for 2); none under REM (CHProgREM.py:977,1123 call
+// base_net.g_s directly)
+const UnetW* decode_filter(const pc_codec* c)
+{
+    if (!c->post_mode || c->rem_n) return nullptr;
+    return &c->unet[c->post_mode == 2 ? 1 : 0];
+}
+
+// g_s, then the post-filter and its clamp when one is loaded (CHProg_cnn.py:909-914, 990-995, 1066-1071, 1181-1184)
+int synth(pc_codec* c, hipStream_t st, const GsW& g, const float* yhat, int B, int h, int w, float* x_hat)
+{
+    PCCHK(g_s(c, st, g, yhat, B, h, w, x_hat));
+    const UnetW* u = decode_filter(c);
+    return u ? unet(c, st, *u, x_hat, B, 16 * h, 16 * w, x_hat, PC_EPI_CLAMP01) : PC_OK;
 }
 
 int h_a(pc_codec* c, hipStream_t st, const float* y, int B, int h, int w, float* z)
@@ -1010,10 +1168,23 @@ extern "C" int pc_codec_finalize(pc_codec* c)
             c->rem_levels_loaded = levels;
         }
     }
+    if (c->post_mode == 1) PCCHK(load_unet(c, "refine", &c->unet[0]));          // CHProg_cnn.py:283-284
+    if (c->post_mode == 2)                                                      // :277-281
+        for (int i = 0; i < 2; ++i) PCCHK(load_unet(c, "refine." + std::to_string(i), &c->unet[i]));
     c->sd.clear();
     c->finalized = true;
     return PC_OK;
 }
+
+extern "C" int pc_codec_set_post_filter(pc_codec* c, int mode)
+{
+    // ChannelProgresssiveWACNN(u_net_post=mode) (CHProg_cnn.py:87-88, 277-284): which refine nets pc_codec_finalize loads
+    if (!c || mode < 0 || mode > 2) return PC_ERR_ARG;
+    if (c->finalized) return PC_ERR_STATE;
+    c->post_mode = mode;
+    return PC_OK;
+}
+
 
 extern "C" int pc_codec_set_scale_table(pc_codec* c, const float* table, int n)
 {
@@ -1832,6 +2003,23 @@ extern "C" int pc_codec_get_level_string(const pc_codec* c, int level, int slice
 // coding -- the likelihood of every quantised latent element under its Gaussian (entropy_models.py:626-659) comes out of the same
 // fused mask / index / quantise kernel, the hyper-latent's from the EntropyBottleneck density network (:400-433) -- followed by the
 // synthesis transform.  x_hat equals decompress(compress(x)) bit for bit (same y_hat); estimated bits = -sum(log2(likelihood)).
+extern "C" int pc_codec_post_filter(pc_codec* c, int which, const float* x, int B, int H, int W, float* out, void* stream)
+{
+    // net.refine(x) (mode 1, which 0) / net.refine[which](x) (mode 2): unclamped, NCHW [B][3][H][W] in and out (out may be x)
+    if (!c || !x || !out || B <= 0 || H <= 0 || W <= 0 || (H % 4) || (W % 4)) return PC_ERR_ARG;
+    if (!c->finalized || !c->post_mode) return PC_ERR_STATE;
+    if (which < 0 || which >= c->post_mode) return PC_ERR_ARG;
+    BusyGuard busy(c);
+    if (!busy.ok) return PC_ERR_STATE;
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = (hipStream_t)stream;
+    CallOrder order(c, st);
+    if (order.rc != PC_OK) return order.rc;
+    g_prof = c->profile ? c : nullptr;
+    g_rowtabs = c->rowtabs;
+    return unet(c, st, c->unet[which], x, B, H, W, out, PC_EPI_NONE);
+}
+
 extern "C" int pc_codec_forward(pc_codec* c, const float* x, int B, int H, int W, double quality, int mask_pol, float* x_hat,
                                 float* y_lik, float* z_lik, float* masks_out, int force_enhanced, void* stream)
 {
@@ -1872,7 +2060,7 @@ extern "C" int pc_codec_forward(pc_codec* c, const float* x, int B, int H, int W
         PCCHK(run_chain(k, st, false, nullptr, nullptr));                                // :1033-1061
         if (enh) PCCHK(run_chain(ke, st, false, nullptr, nullptr));                      // :1089-1160
     }
-    PCCHK(g_s(c, st, c->gs[enh ? 1 : 0], enh ? k.ye : k.yb, B, h, w, x_hat));            // :1065 / :1166-1170
+    PCCHK(synth(c, st, c->gs[enh ? 1 : 0], enh ? k.ye : k.yb, B, h, w, x_hat));            // :1065 / :1166-1170
     return PC_OK;
 }
 
@@ -1960,8 +2148,8 @@ int decompress_impl(pc_codec* c, const uint8_t* const* y_strings, const size_t* 
     if (piped && !rest.empty()) {
         ChainCtx k2;
         PCCHK(second_level_set(c, k, true, &k2));
-        for (int l = 0; l < n_levels; ++l) if (qualities[l] == 0) PCCHK(g_s(c, st, c->gs[0], k.yb, B, h, w, x_hat + (size_t)l * img_elems));   // :907-916
-        PCCHK(g_s(c, st, c->gs[1], k.ye, B, h, w, x_hat + (size_t)first_enh * img_elems));                                               // :986-990
+        for (int l = 0; l < n_levels; ++l) if (qualities[l] == 0) PCCHK(synth(c, st, c->gs[0], k.yb, B, h, w, x_hat + (size_t)l * img_elems));   // :907-916
+        PCCHK(synth(c, st, c->gs[1], k.ye, B, h, w, x_hat + (size_t)first_enh * img_elems));                                               // :986-990
         for (size_t p = 0; p < rest.size(); p += 2) {
             const int la = rest[p], lb = p + 1 < rest.size() ? rest[p + 1] : -1;
             const ChainCtx ka = level_ctx(k2, la, qualities[la], mask_pol);
@@ -1973,21 +2161,21 @@ int decompress_impl(pc_codec* c, const uint8_t* const* y_strings, const size_t* 
                 PCCHK(decode_lane(ka, 0, B, st, "PA", y_strings, y_lens, nt));
             }
             staging_mark.mark();
-            PCCHK(g_s(c, st, c->gs[1], ka.ye, B, h, w, x_hat + (size_t)la * img_elems));
-            if (lb >= 0) PCCHK(g_s(c, st, c->gs[1], k.ye, B, h, w, x_hat + (size_t)lb * img_elems));
+            PCCHK(synth(c, st, c->gs[1], ka.ye, B, h, w, x_hat + (size_t)la * img_elems));
+            if (lb >= 0) PCCHK(synth(c, st, c->gs[1], k.ye, B, h, w, x_hat + (size_t)lb * img_elems));
         }
     } else
     for (int l = 0; l < n_levels; ++l) {
         float* out = x_hat + (size_t)l * img_elems;
         if (qualities[l] == 0) {
-            PCCHK(g_s(c, st, c->gs[0], k.yb, B, h, w, out));                             // :907-916
+            PCCHK(synth(c, st, c->gs[0], k.yb, B, h, w, out));                             // :907-916
             continue;
         }
         if (!(piped && l == first_enh)) {
             PCCHK(run_chain(level_ctx(k, l, qualities[l], mask_pol), st, true, y_strings, y_lens));   // :930-983
             staging_mark.mark();
         }
-        PCCHK(g_s(c, st, c->gs[1], k.ye, B, h, w, out));                                 // :986-990
+        PCCHK(synth(c, st, c->gs[1], k.ye, B, h, w, out));                                 // :986-990
     }
     {
         int n_enh = 0;

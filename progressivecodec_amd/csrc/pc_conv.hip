@@ -64,6 +64,8 @@ __device__ __forceinline__ float epilogue_apply(int epi, float v, float a0, floa
     case PC_EPI_LRP_ADD: return (a0 + 0.5f * pc_tanhf(v)) + a1;
     case PC_EPI_LEAKY: return v > 0.0f ? v : v * 0.01f;
     case PC_EPI_LEAKY_RES: return (v > 0.0f ? v : v * 0.01f) + a0;
+    case PC_EPI_RELU: return v > 0.0f ? v : 0.0f;
+    case PC_EPI_SE_ADD: return v + a0 * a1;               // a1 = the SE scale of (image, channel); two roundings (-ffp-contract=off)
     default: return v;
     }
 }
@@ -136,13 +138,14 @@ __device__ __forceinline__ f32x2 pc_geluf2(f32x2 x)
     return (0.5f * x) * (1.0f + erf);
 }
 
-__device__ __forceinline__ bool epilogue_uses_aux0(int epi) { return epi == PC_EPI_RES_GELU || epi == PC_EPI_RES || epi == PC_EPI_GATE || epi == PC_EPI_GDN || epi == PC_EPI_IGDN || epi == PC_EPI_LRP || epi == PC_EPI_LRP_ADD || epi == PC_EPI_LEAKY_RES; }
+__device__ __forceinline__ bool epilogue_uses_aux0(int epi) { return epi == PC_EPI_RES_GELU || epi == PC_EPI_RES || epi == PC_EPI_GATE || epi == PC_EPI_GDN || epi == PC_EPI_IGDN || epi == PC_EPI_LRP || epi == PC_EPI_LRP_ADD || epi == PC_EPI_LEAKY_RES || epi == PC_EPI_SE_ADD; }
 __device__ __forceinline__ bool epilogue_uses_aux1(int epi) { return epi == PC_EPI_GATE || epi == PC_EPI_LRP_ADD; }
 
 __device__ __forceinline__ float epilogue_value(const pc_conv_params& p, float v, int64_t pix, int n)
 {
     const float a0 = epilogue_uses_aux0(p.epi) ? p.aux0[pix * p.ld0 + n] : 0.0f;
-    const float a1 = epilogue_uses_aux1(p.epi) ? p.aux1[pix * p.ld1 + n] : 0.0f;
+    float a1 = epilogue_uses_aux1(p.epi) ? p.aux1[pix * p.ld1 + n] : 0.0f;
+    if (p.epi == PC_EPI_SE_ADD) a1 = p.aux1[(pix / ((int64_t)p.outH * p.outW)) * p.ld1 + n];   // per (image, channel)
     return epilogue_apply(p.epi, v, a0, a1);
 }
 
@@ -1103,7 +1106,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TM * TN == 
     const uint32_t rowtab_lds_addr = smem_lds + tab_byte0 + (uint32_t)wave * 256u;
     // (the unrolled form is instantiated for the one-tile waves only -- every default instantiation; the two- and four-tile waves, reachable
     // through PC_CONV_TM / PC_CONV_TN for the bit-invariance runs, keep the generic loop: 24 more epilogue bodies per tile otherwise)
-    const bool fast = TM * TN == 1 && p.out_sc == 1 && (p.dense_out || !u0);
+    // (SE_ADD reads its scale per (image, channel): generic tile)
+    const bool fast = TM * TN == 1 && p.out_sc == 1 && (p.dense_out || !u0) && p.epi != PC_EPI_SE_ADD;
     // (dynamic indexing of the kernel-argument struct from inside a lambda makes hipcc copy the whole struct to scratch: hoisted)
     const int ooy_ph = p.ooy[phase], oox_ph = p.oox[phase];
     const float* const aux0_p = p.aux0; const float* const aux1_p = p.aux1;
@@ -1114,6 +1118,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TM * TN == 
               e_outH = p.outH, e_outW = p.outW;
     const int64_t e_sx = p.out_sx, e_sy = p.out_sy, e_sb = p.out_sb, e_sc = p.out_sc;
     const int* const e_rowtab = p.rowtab;
+    float* const e_relu = p.out_relu;                                 // dual store (dense output only, checked by pc_conv_launch)
     auto slow_tile = [&](auto i_tag, auto j_tag) __attribute__((always_inline)) {   // generic form: any output strides, aux tensors read from global memory
         constexpr int i = decltype(i_tag)::value, j = decltype(j_tag)::value;
         const int mb = m0 + wm * 32 * TM + i * 32, nb = n0 + (wn * TN + j) * 32;
@@ -1128,8 +1133,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TM * TN == 
             if (bias) v = v + bv;
             if (e_dense) {
                 opix = e_perm ? (int64_t)e_rowtab[m] : (int64_t)m;
-                v = epilogue_apply(epi_v, v, u0 ? aux0_p[opix * ld0_v + n] : 0.0f, u1 ? aux1_p[opix * ld1_v + n] : 0.0f);
+                const float a1 = epi_v == PC_EPI_SE_ADD ? aux1_p[(opix / HoWo) * ld1_v + n] : (u1 ? aux1_p[opix * ld1_v + n] : 0.0f);
+                v = epilogue_apply(epi_v, v, u0 ? aux0_p[opix * ld0_v + n] : 0.0f, a1);
                 outp[opix * e_sx + (int64_t)n * e_sc] = v;
+                if (e_relu) e_relu[opix * e_sx + (int64_t)n * e_sc] = v > 0.0f ? v : 0.0f;
                 continue;
             }
             const int b = m / HoWo, rr = m - b * HoWo;
@@ -1138,7 +1145,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TM * TN == 
             int nn = n, YY = Y, XX = X;
             if (e_ps) { nn = n >> 2; YY = 2 * Y + ((n >> 1) & 1); XX = 2 * X + (n & 1); }
             const int64_t pix = ((int64_t)b * e_outH + YY) * e_outW + XX;
-            v = epilogue_apply(epi_v, v, u0 ? aux0_p[pix * ld0_v + nn] : 0.0f, u1 ? aux1_p[pix * ld1_v + nn] : 0.0f);
+            v = epilogue_apply(epi_v, v, u0 ? aux0_p[pix * ld0_v + nn] : 0.0f,
+                               epi_v == PC_EPI_SE_ADD ? aux1_p[(int64_t)b * ld1_v + nn] : (u1 ? aux1_p[pix * ld1_v + nn] : 0.0f));
             outp[(int64_t)b * e_sb + (int64_t)YY * e_sy + (int64_t)XX * e_sx + (int64_t)nn * e_sc] = v;
         }
     };
@@ -1184,6 +1192,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TM * TN == 
         // stride, and the range check looks at the vector offset, which holds the row part); table form -- their entry is out of range
         const int rows_live = e_M - mb < 32 ? e_M - mb : 32;
         const __amdgpu_buffer_rsrc_t rs_out = __builtin_amdgcn_make_buffer_rsrc(outp + off0, 0, DIRECT ? (int)((int64_t)rows_live * e_sx * 4) : 0x7fffffff, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rs_relu = __builtin_amdgcn_make_buffer_rsrc(e_relu ? e_relu + off0 : outp + off0, 0,
+                                                                                  DIRECT ? (int)((int64_t)rows_live * e_sx * 4) : 0x7fffffff, 0x00020000);
         // aux tiles: four LDS-DMA loads per tile and tensor into the idle stage buffers -- one memory latency per wave instead of 16
         // dependent global loads, no extra VGPRs
         if (U0) {
@@ -1265,6 +1275,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TM * TN == 
                     if (DIRECT) ro = (uint32_t)(8 * q + e) * sx4;
                     else ro = e == 0 ? rcur.x : (e == 1 ? rcur.y : (e == 2 ? rcur.z : rcur.w));
                     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, o), rs_out, (int)(ro + lane_off), 0, 0);
+                    if (e_relu) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, o > 0.0f ? o : 0.0f), rs_relu, (int)(ro + lane_off), 0, 0);
                     __builtin_amdgcn_sched_barrier(0);                   // one element at a time: interleaved, the 16 GELUs cost 20 VGPRs (one wave per SIMD less); letting the
                                                                          // one-workgroup-per-CU instantiation interleave them changed nothing (profiles/r03_o_*)
                 }
@@ -1339,7 +1350,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TM * TN == 
 #define PC_EPI_CASE(E) case E: if (direct) finish(std::integral_constant<int, E>{}, std::true_type{}); else finish(std::integral_constant<int, E>{}, std::false_type{}); break;
         PC_EPI_CASE(PC_EPI_GELU) PC_EPI_CASE(PC_EPI_RES_GELU) PC_EPI_CASE(PC_EPI_RES) PC_EPI_CASE(PC_EPI_GATE) PC_EPI_CASE(PC_EPI_GDN)
         PC_EPI_CASE(PC_EPI_IGDN) PC_EPI_CASE(PC_EPI_CLAMP01) PC_EPI_CASE(PC_EPI_LRP) PC_EPI_CASE(PC_EPI_LRP_ADD) PC_EPI_CASE(PC_EPI_LEAKY)
-        PC_EPI_CASE(PC_EPI_LEAKY_RES)
+        PC_EPI_CASE(PC_EPI_LEAKY_RES) PC_EPI_CASE(PC_EPI_RELU)
 #undef PC_EPI_CASE
         default: if (direct) finish(std::integral_constant<int, PC_EPI_NONE>{}, std::true_type{}); else finish(std::integral_constant<int, PC_EPI_NONE>{}, std::false_type{}); break;
         }
@@ -1600,7 +1611,7 @@ hipError_t launch_uni(const pc_conv_params& p, hipStream_t stream)
     for (int ph = 0; ph < p.nphase; ++ph) tmax = std::max(tmax, p.ntap[ph]);
     const bool u1 = p.epi == PC_EPI_GATE || p.epi == PC_EPI_LRP_ADD;                         // epilogue_uses_aux1
     const bool u0 = u1 || p.epi == PC_EPI_RES_GELU || p.epi == PC_EPI_RES || p.epi == PC_EPI_GDN || p.epi == PC_EPI_IGDN || p.epi == PC_EPI_LRP ||
-                    p.epi == PC_EPI_LEAKY_RES;                                                 // epilogue_uses_aux0
+                    p.epi == PC_EPI_LEAKY_RES || p.epi == PC_EPI_SE_ADD;                       // epilogue_uses_aux0
     const size_t stage_bytes = (size_t)S * (BM + BN) * (BK / 4) * 16, epi_bytes = !p.dense_out ? 0 : (u1 ? 32768 : (u0 ? 16384 : 0));
     // stages (or the epilogue's aux tiles, whichever is larger), then the run table of the K loop / the epilogue's row tables (256 B per wave)
     const size_t lds = std::max(stage_bytes, epi_bytes) + std::max((size_t)tmax * p.nseg * 2 * sizeof(pc_run), (size_t)1024);
@@ -1703,6 +1714,8 @@ int pc_conv_launch(const pc_conv_params& p_in, hipStream_t stream)
     for (int ph = 0; ph < p.nphase; ++ph)
         if (p.ntap[ph] < 1 || p.ntap[ph] > PC_MAX_TAP) return PC_ERR_ARG;
     if (p.pixel_shuffle && (p.Cout % 4)) return PC_ERR_ARG;
+    if (p.epi == PC_EPI_SE_ADD && (!p.aux0 || !p.aux1 || p.nphase != 1)) return PC_ERR_ARG;
+    if (p.out_relu && (!p.dense_out || p.out_sc != 1 || p.wlayout != 1 || p.ngroup == 2)) return PC_ERR_ARG;   // the unified kernel's dense stores only
 
     // Kernel selection (measured on MI355X with tools/conv_tune.py; profiles/r01_*):
     //  * weight layout 1 (chosen at pack time by pc_conv_weight_layout: Cin % 16 == 0, Cout > 4; GDN's gamma is always layout 1):

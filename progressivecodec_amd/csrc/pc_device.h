@@ -35,6 +35,9 @@ enum {
     PC_EPI_LRP_ADD = 9,   // (y_hat + 0.5 * tanh(lrp)) + base  (merge "res")      CHProg_cnn.py:837-843
     PC_EPI_LEAKY = 10,    // nn.LeakyReLU() (slope 0.01)                          models/utils.py:65,79
     PC_EPI_LEAKY_RES = 11,// ResidualBlock tail: leaky(conv2) + identity          models/utils.py:80-86
+    PC_EPI_RELU = 12,     // nn.ReLU: v > 0 ? v : 0                               layers/unet.py:15-16,35
+    PC_EPI_SE_ADD = 13,   // ConvBlockResidual: up_dim(x) + conv_out * s[b, c]    layers/unet.py:50-52,67-70
+                          //   (v + aux0[p, n] * aux1[b * ld1 + n]: product rounded, then the add; aux1 = the SE scales [B][Cout])
 };
 
 enum { PC_TILE_AUTO = 0, PC_TILE_128x128 = 1, PC_TILE_64x64 = 2, PC_TILE_128x32 = 3 };
@@ -71,6 +74,8 @@ struct pc_conv_params {
     int64_t out_sb, out_sy, out_sx, out_sc;  // generic output strides (NHWC slice or NCHW)
     float* out;
     int pixel_shuffle;                       // PixelShuffle(2) folded into the store
+    float* out_relu;                         // optional second store: relu(value) at the same offsets as `out` (dense NHWC output only):
+                                             // the ResBlock's leading ReLU of the next block, the un-activated value stays the identity
     // epilogue
     int epi;
     const float* aux0; int ld0;
@@ -143,6 +148,14 @@ size_t pc_quantile_work_bytes(int B);
 // mu != null: the mu_std form -- ret has 2N channels per pixel, mu <- ret[:N] * att + mu as well (:397-398,414-416)
 int pc_rem_combine_launch(const float* ret, int ld_ret, float* scale, int ld_scale, int B, int HW, const float* thr_star, int mode_star,
                           const float* thr_bar, int mode_bar, hipStream_t stream, float* mu = nullptr, int ld_mu = 0);
+// UNet post-filter (layers/unet.py): SELayer squeeze and MaxPool2d(2)
+// SE squeeze of an NHWC [B][HW][C] tensor (C in 16 / 32 / 64 / 128): mean over HW in the fixed order of DESIGN.md section 2 (chunks of
+// PC_SE_CHUNK pixels, G = 1024 / C pixel groups per chunk), then s = sigmoid(fc2 . relu(fc1 . mean)); fc1 [C/16][C], fc2 [C][C/16] as
+// nn.Linear stores them.  part: [B][ceil(HW / PC_SE_CHUNK)][C] scratch; s: [B][C]
+#define PC_SE_CHUNK 4096
+int pc_se_squeeze_launch(const float* x, int B, int HW, int C, const float* fc1, const float* fc2, float* part, float* s, hipStream_t stream);
+// MaxPool2d(2) NHWC [B][H][W][C] -> [B][H/2][W/2][C] (C % 4 == 0, H and W even); the window's max taken as ATen's CPU kernel does
+int pc_maxpool2_launch(const float* x, int B, int H, int W, int C, float* out, hipStream_t stream);
 // one C-channel slice of an NCHW tensor (element (b, c, p) at src[b * batch_stride + c * HW + p]) -> NHWC [B][HW][C]
 int pc_nchw_slice_to_nhwc_launch(const float* src, int64_t batch_stride, int B, int HW, int C, float* dst, hipStream_t stream);
 

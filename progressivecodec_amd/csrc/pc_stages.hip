@@ -959,3 +959,116 @@ int pc_nchw_slice_to_nhwc_launch(const float* src, int64_t batch_stride, int B, 
     hipLaunchKernelGGL(nchw_slice_to_nhwc_kernel, dim3(blocks), dim3(256), 0, stream, src, batch_stride, B, HW, C, dst);
     return PC_LAUNCH_CHECK();
 }
+
+// ------------------------------------------------------------------------------------------ UNet post-filter (layers/unet.py)
+namespace {
+
+// SELayer squeeze, pass 1 (unet.py:46-47, torch.mean over H x W): one workgroup per (chunk of PC_SE_CHUNK pixels, image).  Thread
+// (g, q) -- G = 1024 / C pixel groups x C / 4 channel quads -- sums pixels g, g + G, g + 2G ... of the chunk in ascending order from +0
+// (one add chain per channel); the G partials of a channel are then added in ascending g from +0.  The order depends on C and HW only:
+// never on B, the grid or the device.
+__global__ __launch_bounds__(256) void se_partial_kernel(const float* __restrict__ x, int HW, int C, int nchunk, float* __restrict__ part)
+{
+    __shared__ float red[1024];
+    const int Q = C >> 2, G = 256 / Q;
+    const int tid = threadIdx.x, g = tid / Q, q = tid - g * Q;
+    const int k = blockIdx.x, b = blockIdx.y;
+    const int p0 = k * PC_SE_CHUNK, p1 = min(p0 + PC_SE_CHUNK, HW);
+    const float* xb = x + (int64_t)b * HW * C + 4 * q;
+    float4 acc = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    for (int p = p0 + g; p < p1; p += G) {
+        const float4 v = *reinterpret_cast<const float4*>(xb + (int64_t)p * C);
+        acc.x = acc.x + v.x; acc.y = acc.y + v.y; acc.z = acc.z + v.z; acc.w = acc.w + v.w;
+    }
+    red[g * C + 4 * q + 0] = acc.x; red[g * C + 4 * q + 1] = acc.y; red[g * C + 4 * q + 2] = acc.z; red[g * C + 4 * q + 3] = acc.w;
+    __syncthreads();
+    if (tid < C) {
+        float t = 0.0f;
+        for (int gg = 0; gg < G; ++gg) t = t + red[gg * C + tid];
+        part[((int64_t)b * nchunk + k) * C + tid] = t;
+    }
+}
+
+// pass 2, one workgroup per image: the chunk sums added in ascending chunk order from +0, divided by HW (correctly rounded); then
+// fc.0 (C -> C/16), ReLU, fc.2 (C/16 -> C), sigmoid (unet.py:37-43).  Each FC output is one fmaf chain from +0 over its inputs in the
+// conv contract's order (aligned groups of 8 visited 0,4,1,5,2,6,3,7, absent k skipped), no bias.
+__global__ __launch_bounds__(128) void se_excite_kernel(const float* __restrict__ part, int nchunk, int HW, int C, const float* __restrict__ fc1,
+                                                        const float* __restrict__ fc2, float* __restrict__ s)
+{
+    __shared__ float mean[128], hid[8];
+    const int tid = threadIdx.x, b = blockIdx.x, R = C >> 4;
+    if (tid < C) {
+        float t = 0.0f;
+        for (int k = 0; k < nchunk; ++k) t = t + part[((int64_t)b * nchunk + k) * C + tid];
+        mean[tid] = t / (float)HW;
+    }
+    __syncthreads();
+    if (tid < R) {
+        float h = 0.0f;
+        for (int k0 = 0; k0 < C; k0 += 8)
+            for (int e = 0; e < 8; ++e) {
+                const int kk = k0 + (e >> 1) + 4 * (e & 1);
+                if (kk < C) h = fmaf(mean[kk], fc1[tid * C + kk], h);
+            }
+        hid[tid] = h > 0.0f ? h : 0.0f;
+    }
+    __syncthreads();
+    if (tid < C) {
+        float z = 0.0f;
+        for (int k0 = 0; k0 < R; k0 += 8)
+            for (int e = 0; e < 8; ++e) {
+                const int kk = k0 + (e >> 1) + 4 * (e & 1);
+                if (kk < R) z = fmaf(hid[kk], fc2[tid * R + kk], z);
+            }
+        s[(int64_t)b * C + tid] = pc_sigmoidf(z);
+    }
+}
+
+// MaxPool2d(2) (unet.py:74), NHWC, one thread per output float4.  The window is visited (0,0) (0,1) (1,0) (1,1) and a value replaces the
+// running max when it is larger or NaN -- ATen's CPU max_pool2d rule
+__device__ __forceinline__ float pool_take(float m, float v) { return (v > m || v != v) ? v : m; }
+__global__ __launch_bounds__(256) void maxpool2_kernel(const float* __restrict__ x, int B, int H, int W, int C, float* __restrict__ out)
+{
+    const int Ho = H >> 1, Wo = W >> 1, Q = C >> 2;
+    const int64_t n = (int64_t)B * Ho * Wo * Q;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const int q = (int)(i % Q);
+        const int64_t pix = i / Q;
+        const int ox = (int)(pix % Wo), oy = (int)((pix / Wo) % Ho);
+        const int64_t b = pix / ((int64_t)Wo * Ho);
+        const float* p00 = x + (((b * H + 2 * oy) * W + 2 * ox) * C + 4 * q);
+        const float4 v0 = *reinterpret_cast<const float4*>(p00);
+        const float4 v1 = *reinterpret_cast<const float4*>(p00 + C);
+        const float4 v2 = *reinterpret_cast<const float4*>(p00 + (int64_t)W * C);
+        const float4 v3 = *reinterpret_cast<const float4*>(p00 + (int64_t)W * C + C);
+        float4 m;
+        m.x = pool_take(pool_take(pool_take(v0.x, v1.x), v2.x), v3.x);
+        m.y = pool_take(pool_take(pool_take(v0.y, v1.y), v2.y), v3.y);
+        m.z = pool_take(pool_take(pool_take(v0.z, v1.z), v2.z), v3.z);
+        m.w = pool_take(pool_take(pool_take(v0.w, v1.w), v2.w), v3.w);
+        *reinterpret_cast<float4*>(out + pix * C + 4 * q) = m;
+    }
+}
+
+}  // namespace
+
+int pc_se_squeeze_launch(const float* x, int B, int HW, int C, const float* fc1, const float* fc2, float* part, float* s, hipStream_t stream)
+{
+    if (!x || !fc1 || !fc2 || !part || !s || B <= 0 || HW <= 0 || B > 65535) return PC_ERR_ARG;
+    if (C != 16 && C != 32 && C != 64 && C != 128) return PC_ERR_ARG;
+    if (((uintptr_t)x & 15)) return PC_ERR_ARG;
+    const int nchunk = (HW + PC_SE_CHUNK - 1) / PC_SE_CHUNK;
+    hipLaunchKernelGGL(se_partial_kernel, dim3(nchunk, B), dim3(256), 0, stream, x, HW, C, nchunk, part);
+    hipLaunchKernelGGL(se_excite_kernel, dim3(B), dim3(128), 0, stream, part, nchunk, HW, C, fc1, fc2, s);
+    return PC_LAUNCH_CHECK();
+}
+
+int pc_maxpool2_launch(const float* x, int B, int H, int W, int C, float* out, hipStream_t stream)
+{
+    if (!x || !out || B <= 0 || H < 2 || W < 2 || (H & 1) || (W & 1) || C <= 0 || (C & 3)) return PC_ERR_ARG;
+    if (((uintptr_t)x & 15) || ((uintptr_t)out & 15)) return PC_ERR_ARG;
+    const int64_t n = (int64_t)B * (H / 2) * (W / 2) * (C / 4);
+    const int blocks = (int)((n + 255) / 256 < 8192 ? (n + 255) / 256 : 8192);
+    hipLaunchKernelGGL(maxpool2_kernel, dim3(blocks), dim3(256), 0, stream, x, B, H, W, C, out);
+    return PC_LAUNCH_CHECK();
+}

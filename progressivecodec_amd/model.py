@@ -19,7 +19,7 @@ from .arch import CodecConfig, param_spec
 
 _MASK_POL = {"point-based-std": 0, "two-levels": 1, "three-levels-std": 2}
 _PARAM_KINDS = {"conv_w", "conv_b", "deconv_w", "linear_w", "gdn_beta", "gdn_gamma", "relpos_table", "eb_matrix", "eb_bias", "eb_factor",
-                "eb_quantiles"}          # arch.param_spec kinds that are nn.Parameters in the reference (the rest are buffers)
+                "eb_quantiles", "unet_conv_w", "unet_conv_b", "unet_linear_w"}          # arch.param_spec kinds that are nn.Parameters in the reference (the rest are buffers)
 _DT = {"float32": 0, "int32": 1, "int64": 2}
 
 
@@ -53,14 +53,15 @@ class ChannelProgresssiveWACNN(_module_base()):
 
     def __init__(self, N=192, M=640, division_dimension=(320, 640), dim_chunk=32, multiple_decoder=True,
                  multiple_encoder=False, multiple_hyperprior=True, mask_policy="two-levels", lmbda_list=(0.0055, 0.04),
-                 joiner_policy="res", support_progressive_slices=5, delta_encode=True, device="cuda:0", **kwargs):
+                 joiner_policy="res", support_progressive_slices=5, delta_encode=True, u_net_post=0, device="cuda:0", **kwargs):
         super().__init__()
         self.cfg = CodecConfig(N=N, M=M, division_dimension=tuple(division_dimension), dim_chunk=dim_chunk,
                                multiple_decoder=multiple_decoder, multiple_encoder=multiple_encoder,
                                multiple_hyperprior=multiple_hyperprior, delta_encode=delta_encode,
                                joiner_policy=joiner_policy, support_progressive_slices=support_progressive_slices,
-                               mask_policy=mask_policy)
+                               mask_policy=mask_policy, u_net_post=u_net_post)
         self.cfg.check_supported()
+        self.u_net_post = u_net_post
         self.mask_policy = mask_policy
         self.lmbda_list = list(lmbda_list)
         import torch
@@ -170,6 +171,7 @@ class ChannelProgresssiveWACNN(_module_base()):
             check(lib().pc_codec_set_tensor(self._h, k.encode(), a.ctypes.data_as(C.c_void_p), _DT[dtype], shp, a.ndim),
                   f"set_tensor({k})")
         self._sd = sd
+        check(lib().pc_codec_set_post_filter(self._h, self.cfg.u_net_post), "pc_codec_set_post_filter")
         check(lib().pc_codec_finalize(self._h), "pc_codec_finalize")
         self._finalized = True
         for which, p in ((0, "gaussian_conditional"), (1, "entropy_bottleneck")):
@@ -207,6 +209,26 @@ class ChannelProgresssiveWACNN(_module_base()):
             self._set_tables(1, entropy.entropy_bottleneck_tables(self._sd))
             updated = True
         return updated
+
+    def post_filter(self, x, which=None):
+        """``net.refine(x)`` (u_net_post=1) or ``net.refine[which](x)`` (u_net_post=2; default which=1, the net every decode path uses):
+        the UNet post-filter alone, unclamped, on a [B, 3, H, W] device tensor with H and W multiples of 4 (CHProg_cnn.py:277-284)."""
+        import torch
+        if not self.cfg.u_net_post:
+            raise RuntimeError("this model has no post-filter (u_net_post=0)")
+        if not self._finalized:
+            raise ValueError("load_state_dict() first")
+        if which is None:
+            which = 1 if self.cfg.u_net_post == 2 else 0
+        if x.dim() != 4 or x.shape[1] != 3:
+            raise ValueError(f"post_filter expects a [B, 3, H, W] tensor, got {tuple(x.shape)}")
+        xi = x.to(self.device, torch.float32).contiguous()
+        out = torch.empty_like(xi)
+        B, _, H, W = xi.shape
+        with self._call_lock:
+            check(lib().pc_codec_post_filter(self._h, int(which), C.c_void_p(xi.data_ptr()), B, H, W, C.c_void_p(out.data_ptr()), self._stream()),
+                  "pc_codec_post_filter")
+        return out
 
     def set_option(self, name, value):
         """pc_codec_set_option: schedule options of this object ("serial_schedule", "lanes_enc", "lanes_dec", "host_threads") -- results never

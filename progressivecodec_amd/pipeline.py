@@ -85,7 +85,7 @@ class CodecPipeline:
                                 multiple_decoder=_encoder.cfg.multiple_decoder, multiple_encoder=_encoder.cfg.multiple_encoder,
                                 multiple_hyperprior=_encoder.cfg.multiple_hyperprior, mask_policy=_encoder.mask_policy,
                                 joiner_policy=_encoder.cfg.joiner_policy, support_progressive_slices=_encoder.cfg.support_progressive_slices,
-                                delta_encode=_encoder.cfg.delta_encode)
+                                delta_encode=_encoder.cfg.delta_encode, u_net_post=_encoder.cfg.u_net_post)
         else:
             if state_dict is None:
                 raise ValueError("CodecPipeline needs a state dict (or use CodecPipeline.from_model)")

@@ -25,6 +25,9 @@ _PED = float((2.0 ** -18) ** 2)  # parametrizers.py:27-30
 # amplification recipe (tuned through the real reference: index histogram 0..27, bypass rate ~0.3 %)
 AMP_Y, AMP_Z, AMP_S, BIAS_S = 0.8, 4.0, 2.0, 0.6
 AMP_HS, AMP_M = 0.15, 1.0
+# UNet post-filter (refine.*): fan-in scaled, the trailing conv3x3(16, 3) damped and centred so that the filtered image stays mostly inside
+# (0, 1) -- the clamp must leave real work to the filter (tests/test_unet_post_host.py checks the share)
+UNET_OUT_AMP, UNET_OUT_BIAS = 0.25, 0.5
 
 
 def _rng(name: str, seed: int):
@@ -124,6 +127,17 @@ def synthetic_state_dict(cfg: CodecConfig = CodecConfig(), seed: int = 0, as_tor
             v = np.full(shape, cfg.scales_min)
         elif kind == "scale_table":
             v = scale_table(cfg)
+        elif kind == "unet_conv_w":
+            co, ci, kh, kw = shape
+            v = g.standard_normal(shape) * math.sqrt(1.0 / (ci * kh * kw))
+            if name.endswith(".1.weight"):
+                v = v * UNET_OUT_AMP
+        elif kind == "unet_conv_b":
+            v = g.standard_normal(shape) * 0.05
+            if name.endswith(".1.bias"):
+                v = v + UNET_OUT_BIAS
+        elif kind == "unet_linear_w":
+            v = g.standard_normal(shape) * math.sqrt(1.0 / shape[1])
         elif kind == "table":
             v = np.zeros([d for d in shape], dtype=np.int32)
         else:
