@@ -231,6 +231,29 @@ PC_API int pc_codec_set_post_filter(pc_codec* c, int mode);
  * must be multiples of 4 (PC_ERR_ARG otherwise, where the reference fails in torch.cat); PC_ERR_STATE without a filter.  Scratch: 864
  * bytes per pixel of the batch, kept by the object (section 6 of DESIGN.md). */
 PC_API int pc_codec_post_filter(pc_codec* c, int which, const float* x, int B, int H, int W, float* out, void* stream);
+/* The single-rate model WACNN (models/cnn.py:23-340; "cnn" in the reference's registry, models/__init__.py) -- the "base" anchor curve
+ * of the paper (training/train.py:379-380).  pc_codec_set_model(c, PC_MODEL_WACNN) before pc_codec_finalize switches the object to that
+ * model's state dict: g_a.<layer> (3 -> 320), g_s.<layer>, h_a.0 = conv3x3(320, 320), h_mean_s.<layer> / h_scale_s.<layer> (one pair,
+ * not a ModuleList), the ten cc_mean / cc_scale / lrp stacks, the EntropyBottleneck and GaussianConditional buffers; finalize returns
+ * PC_ERR_MISSING if one is absent.  PC_MODEL_CHANNEL (the default) is ChannelProgresssiveWACNN.  PC_ERR_STATE after finalize, or for
+ * PC_MODEL_WACNN with a post-filter set.  The progressive entry points (compress, _levels, decompress, _levels, _packed, forward,
+ * post_filter, set_rem, set_cust_map, set_rem_checkpoint) return PC_ERR_STATE on a WACNN object, the pc_codec_wacnn_* ones on a
+ * ChannelProgresssiveWACNN object.  The schedule options keep their meaning for the encoder chain (serial_schedule, lanes_enc) and do
+ * not apply to the decoder, which decodes one stream on the caller's stream and thread; no byte or x_hat depends on them. */
+enum { PC_MODEL_CHANNEL = 0, PC_MODEL_WACNN = 1 };
+PC_API int pc_codec_set_model(pc_codec* c, int kind);
+/* WACNN.compress (cnn.py:214-271): x device NCHW [B][3][H][W], H and W multiples of 64.  Leaves ONE y string for the whole batch --
+ * every symbol of every slice and image in one BufferedRansEncoder stream, slice-major, then image, then C,H,W -- read with
+ * pc_codec_get_string(c, 0, 0, ...), and B z strings (slice = -1).  pc_codec_num_slices returns 1. */
+PC_API int pc_codec_wacnn_compress(pc_codec* c, const float* x, int B, int H, int W, void* stream);
+/* WACNN.decompress (cnn.py:293-340): y = the batch's y string, z_strings / z_lens: B strings, zh, zw = "shape"; x_hat device NCHW
+ * [B][3][64*zh][64*zw], clamped to [0,1].  A y string that does not end exactly where the batch's symbols do (another batch size or
+ * shape, truncated or damaged) returns PC_ERR_TRUNCATED; the check is on the host, after the stream has been decoded. */
+PC_API int pc_codec_wacnn_decompress(pc_codec* c, const uint8_t* y, size_t y_len, const uint8_t* const* z_strings, const size_t* z_lens,
+                                     int B, int zh, int zw, float* x_hat, void* stream);
+/* WACNN.forward in eval mode (cnn.py:145-192): x_hat device [B][3][H][W] = g_s(y_hat) UNCLAMPED, y_lik [B][320][H/16][W/16],
+ * z_lik [B][192][H/64][W/64]; y_hat and z_hat are those of compress.  Needs the entropy_bottleneck._matrix/_bias/_factor tensors. */
+PC_API int pc_codec_wacnn_forward(pc_codec* c, const float* x, int B, int H, int W, float* x_hat, float* y_lik, float* z_lik, void* stream);
 PC_API int pc_codec_num_slices(const pc_codec* c);
 /* string of y slice `slice` (0..n_slices-1) or of z (slice = -1) for image b */
 PC_API int pc_codec_get_string(const pc_codec* c, int slice, int b, const uint8_t** data, size_t* len);

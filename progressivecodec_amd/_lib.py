@@ -23,6 +23,7 @@ EXPORTS = [
     "pc_codec_decompress_packed", "pc_host_pool_plan", "pc_rans_decode_stream", "pc_codec_set_scale_table", "pc_codec_profile_bytes", "pc_contract_id", "pc_rans_decode_batch_u8", "pc_codec_set_rem",
     "pc_codec_host_stats", "pc_codec_set_rem_checkpoint", "pc_codec_set_option", "pc_selftest_packed_gelu", "pc_profile_set_epoch", "pc_codec_profile_intervals",
     "pc_codec_set_post_filter", "pc_codec_post_filter",
+    "pc_codec_set_model", "pc_codec_wacnn_compress", "pc_codec_wacnn_decompress", "pc_codec_wacnn_forward",
 ]
 
 
@@ -92,6 +93,10 @@ def lib():
         L.pc_codec_set_rem_checkpoint.argtypes = [vp, vp]
         L.pc_codec_set_post_filter.argtypes = [vp, C.c_int]
         L.pc_codec_post_filter.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp]
+        L.pc_codec_set_model.argtypes = [vp, C.c_int]
+        L.pc_codec_wacnn_compress.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp]
+        L.pc_codec_wacnn_decompress.argtypes = [vp, vp, sz, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]
+        L.pc_codec_wacnn_forward.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
         L.pc_codec_strings_size.argtypes = [vp, C.POINTER(sz), C.POINTER(C.c_int)]
         L.pc_codec_copy_strings.argtypes = [vp, vp, sz, vp, sz]
         L.pc_codec_decompress_packed.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, vp]

@@ -77,6 +77,7 @@ struct DevBuf { void* p = nullptr; size_t bytes = 0; };
 
 struct pc_codec {
     int device = 0;
+    int model = PC_MODEL_CHANNEL;                // pc_codec_set_model: which reference model the tensors and entry points are
     bool finalized = false;
     std::atomic<bool> busy{false};               // a compress / decompress / forward call is inside: the object is not re-entrant
     hipEvent_t call_done = nullptr;              // recorded on the caller's stream when a call returns; the next call's stream waits for it
@@ -627,8 +628,9 @@ int g_a(pc_codec* c, hipStream_t st, const float* x, int B, int H, int W, float*
     return g_a_net(c, st, c->ga[1], x, B, H, W, y + D0, MLAT);
 }
 
-// g_s[k] (CHProg_cnn.py:149-161): y_hat [B][h][w][320] -> x_hat NCHW [B][3][16h][16w], clamped to [0,1]
-int g_s(pc_codec* c, hipStream_t st, const GsW& g, const float* yhat, int B, int h, int w, float* x_hat)
+// g_s[k] (CHProg_cnn.py:149-161): y_hat [B][h][w][320] -> x_hat NCHW [B][3][16h][16w], clamped to [0,1] (epi PC_EPI_CLAMP01) or
+// not (PC_EPI_NONE: WACNN.forward, models/cnn.py:186)
+int g_s(pc_codec* c, hipStream_t st, const GsW& g, const float* yhat, int B, int h, int w, float* x_hat, int epi = PC_EPI_CLAMP01)
 {
     float *t0, *t1, *t2;
     PCCHK(c->buf("gs_t0", (size_t)B * h * w * D0, &t0));
@@ -654,7 +656,7 @@ int g_s(pc_codec* c, hipStream_t st, const GsW& g, const float* yhat, int B, int
         q.Ho = H; q.Wo = W; q.outH = 2 * H; q.outW = 2 * W; q.M = B * H * W;
         q.pixel_shuffle = 1;
         q.out = x_hat; q.out_sx = 1; q.out_sy = q.outW; q.out_sc = (int64_t)q.outH * q.outW; q.out_sb = 3 * q.out_sc;
-        q.epi = PC_EPI_CLAMP01;
+        q.epi = epi;
         PCCHK(launch_conv(q, st));
     }
     return PC_OK;
@@ -778,7 +780,7 @@ int h_a(pc_codec* c, hipStream_t st, const float* y, int B, int h, int w, float*
     float *t0, *t1;
     PCCHK(c->buf("ha_t0", (size_t)B * h * w * 320, &t0));
     PCCHK(c->buf("ha_t1", (size_t)B * h * w * 288, &t1));
-    PCCHK(conv(st, c->ha[0], {{y, MLAT, MLAT}}, B, h, w, 1, t0, 320, PC_EPI_GELU));
+    PCCHK(conv(st, c->ha[0], {{y, MLAT, c->ha[0].Cin}}, B, h, w, 1, t0, 320, PC_EPI_GELU));   // 640 channels, or WACNN's 320 (cnn.py:58)
     PCCHK(conv(st, c->ha[1], {{t0, 320, 320}}, B, h, w, 1, t1, 288, PC_EPI_GELU));
     PCCHK(conv(st, c->ha[2], {{t1, 288, 288}}, B, h, w, 2, t0, 256, PC_EPI_GELU));
     PCCHK(conv(st, c->ha[3], {{t0, 256, 256}}, B, h / 2, w / 2, 1, t1, 224, PC_EPI_GELU));
@@ -1052,11 +1054,11 @@ extern "C" int pc_codec_set_option(pc_codec* c, const char* name, int value)
     return PC_OK;
 }
 
-extern "C" int pc_codec_finalize(pc_codec* c)
+namespace {
+
+// the transforms of ChannelProgresssiveWACNN (CHProg_cnn.py:131-274)
+int load_channel(pc_codec* c)
 {
-    if (!c) return PC_ERR_ARG;
-    if (c->finalized) return PC_OK;
-    HIPCHK(hipSetDevice(c->device));
     c->multi_enc = c->sd.count("g_a.0.0.weight") != 0;                  // ModuleList of two encoders: keys g_a.<k>.<layer>...
     for (int k = 0; k < (c->multi_enc ? 2 : 1); ++k) {
         const std::string p = c->multi_enc ? "g_a." + std::to_string(k) : std::string("g_a");
@@ -1100,6 +1102,56 @@ extern "C" int pc_codec_finalize(pc_codec* c)
         PCCHK(load_stack5(c, "cc_scale_transforms_prog" + s, D0 + 32 * std::min(i + 1, 6), &c->cc_scale_p[i]));
         PCCHK(load_stack5(c, "lrp_transforms_prog" + s, D0 + 32 * std::min(i + 2, 7), &c->lrp_p[i]));
     }
+    return PC_OK;
+}
+
+// the transforms of WACNN (models/cnn.py:34-134): one 3 -> 320 encoder, one synthesis transform, h_a from 320 channels, one hyper-synthesis
+// pair and the ten base stacks -- the keys are not indexed by a ModuleList where ChannelProgresssiveWACNN's are (g_s.<layer>, h_mean_s.<layer>).
+// The nets go into the slots the progressive model's base path uses (ga[0], gs[0], hms[0] / hss[0]), so the shared launch helpers run them.
+int load_wacnn(pc_codec* c)
+{
+    c->multi_enc = false;
+    pc_codec::GaW& g = c->ga[0];
+    PCCHK(load_conv(c, "g_a.0", 3, NCH, 5, 0, &g.c0));
+    PCCHK(load_gdn(c, "g_a.1", NCH, &g.g1));
+    PCCHK(load_conv(c, "g_a.2", NCH, NCH, 5, 0, &g.c2));
+    PCCHK(load_gdn(c, "g_a.3", NCH, &g.g3));
+    PCCHK(load_wam(c, "g_a.4", NCH, 8, 4, &g.w4));
+    PCCHK(load_conv(c, "g_a.5", NCH, NCH, 5, 0, &g.c5));
+    PCCHK(load_gdn(c, "g_a.6", NCH, &g.g6));
+    PCCHK(load_conv(c, "g_a.7", NCH, D0, 5, 0, &g.c7));
+    PCCHK(load_wam(c, "g_a.8", D0, 4, 2, &g.w8));
+    GsW& s = c->gs[0];
+    PCCHK(load_wam(c, "g_s.0", D0, 4, 2, &s.w0));
+    PCCHK(load_conv(c, "g_s.1", D0, NCH, 5, 1, &s.d1));
+    PCCHK(load_gdn(c, "g_s.2", NCH, &s.g2));
+    PCCHK(load_conv(c, "g_s.3", NCH, NCH, 5, 1, &s.d3));
+    PCCHK(load_gdn(c, "g_s.4", NCH, &s.g4));
+    PCCHK(load_wam(c, "g_s.5", NCH, 8, 4, &s.w5));
+    PCCHK(load_conv(c, "g_s.6", NCH, NCH, 5, 1, &s.d6));
+    PCCHK(load_gdn(c, "g_s.7", NCH, &s.g7));
+    PCCHK(load_deconv3_subpixel(c, "g_s.8", NCH, &s.d8));
+    const int ha_c[6] = {D0, 320, 288, 256, 224, NCH};
+    for (int j = 0; j < 5; ++j) PCCHK(load_conv(c, "h_a." + std::to_string(2 * j), ha_c[j], ha_c[j + 1], 3, 0, &c->ha[j]));
+    PCCHK(load_hs(c, "h_mean_s", &c->hms[0]));
+    PCCHK(load_hs(c, "h_scale_s", &c->hss[0]));
+    for (int i = 0; i < NS0; ++i) {
+        const std::string s5 = "." + std::to_string(i);
+        PCCHK(load_stack5(c, "cc_mean_transforms" + s5, D0 + 32 * std::min(i, 5), &c->cc_mean[i]));
+        PCCHK(load_stack5(c, "cc_scale_transforms" + s5, D0 + 32 * std::min(i, 5), &c->cc_scale[i]));
+        PCCHK(load_stack5(c, "lrp_transforms" + s5, D0 + 32 * std::min(i + 1, 6), &c->lrp[i]));
+    }
+    return PC_OK;
+}
+
+}  // namespace
+
+extern "C" int pc_codec_finalize(pc_codec* c)
+{
+    if (!c) return PC_ERR_ARG;
+    if (c->finalized) return PC_OK;
+    HIPCHK(hipSetDevice(c->device));
+    PCCHK(c->model == PC_MODEL_WACNN ? load_wacnn(c) : load_channel(c));
     {   // EntropyBottleneck medians = quantiles[:, 0, 1]  (entropy_models.py:350)
         const HostTensor* q = find(c, "entropy_bottleneck.quantiles", PC_F32, {NCH, 1, 3});
         if (!q) return PC_ERR_MISSING;
@@ -1139,7 +1191,7 @@ extern "C" int pc_codec_finalize(pc_codec* c)
         if (!b) return PC_ERR_MISSING;
         c->scale_bound = reinterpret_cast<const float*>(b->data.data())[0];
     }
-    {   // REM weights, if the caller set them (keys post_latent.<level>.<slice>.<subnet>.<block>...): 2 or 3 blocks per sub-net
+    if (c->model == PC_MODEL_CHANNEL) {   // REM weights, if the caller set them (keys post_latent.<level>.<slice>.<subnet>.<block>...): 2 or 3 blocks per sub-net
         // ("middle" / "big"), enc one more
         int levels = 0;
         while (levels < 3 && c->sd.count("post_latent." + std::to_string(levels) + ".0.enc.0.conv1.weight")) ++levels;
@@ -1176,11 +1228,20 @@ extern "C" int pc_codec_finalize(pc_codec* c)
     return PC_OK;
 }
 
+extern "C" int pc_codec_set_model(pc_codec* c, int kind)
+{
+    // the reference registry (models/__init__.py): "channel" = ChannelProgresssiveWACNN (default), "cnn" = WACNN; before pc_codec_finalize
+    if (!c || (kind != PC_MODEL_CHANNEL && kind != PC_MODEL_WACNN)) return PC_ERR_ARG;
+    if (c->finalized || (kind == PC_MODEL_WACNN && c->post_mode)) return PC_ERR_STATE;
+    c->model = kind;
+    return PC_OK;
+}
+
 extern "C" int pc_codec_set_post_filter(pc_codec* c, int mode)
 {
     // ChannelProgresssiveWACNN(u_net_post=mode) (CHProg_cnn.py:87-88, 277-284): which refine nets pc_codec_finalize loads
     if (!c || mode < 0 || mode > 2) return PC_ERR_ARG;
-    if (c->finalized) return PC_ERR_STATE;
+    if (c->finalized || (mode && c->model != PC_MODEL_CHANNEL)) return PC_ERR_STATE;
     c->post_mode = mode;
     return PC_OK;
 }
@@ -1207,7 +1268,7 @@ extern "C" int pc_codec_set_rem(pc_codec* c, const double* check_levels, int n_l
     // PostRateProcessedNetwork(base_net, check_levels) (CHProgREM.py:207-235): from now on compress / decompress refine the predicted
     // scale of every enhancement slice with the LatentRateReduction net of the quality's range; n_levels = 0 switches it off again
     if (!c || n_levels < 0 || n_levels > 3 || (n_levels && !check_levels)) return PC_ERR_ARG;
-    if (n_levels && (!c->finalized || c->rem_levels_loaded < n_levels)) return PC_ERR_STATE;
+    if (n_levels && (!c->finalized || c->rem_levels_loaded < n_levels || c->model != PC_MODEL_CHANNEL)) return PC_ERR_STATE;
     for (int i = 0; i + 1 < n_levels; ++i) if (!(check_levels[i] < check_levels[i + 1])) return PC_ERR_ARG;
     c->rem_n = n_levels;
     for (int i = 0; i < n_levels; ++i) c->rem_check[i] = check_levels[i];
@@ -1217,6 +1278,7 @@ extern "C" int pc_codec_set_rem(pc_codec* c, const double* check_levels, int n_l
 extern "C" int pc_codec_set_cust_map(pc_codec* c, const float* cust_map)
 {
     if (!c) return PC_ERR_ARG;
+    if (cust_map && c->model != PC_MODEL_CHANNEL) return PC_ERR_STATE;
     c->cust_map = cust_map;
     return PC_OK;
 }
@@ -1225,6 +1287,7 @@ extern "C" int pc_codec_set_rem_checkpoint(pc_codec* c, const float* rep)
 {
     // checkpoint_rep of PostRateProcessedNetwork.compress / decompress (CHProgREM.py:676,773 / :901,989): consumed by the next call
     if (!c) return PC_ERR_ARG;
+    if (rep && c->model != PC_MODEL_CHANNEL) return PC_ERR_STATE;
     c->rem_ckpt = rep;
     return PC_OK;
 }
@@ -1236,6 +1299,7 @@ extern "C" int pc_codec_get_string(const pc_codec* c, int slice, int b, const ui
     if (!c || !data || !len || b < 0 || b >= c->res_B) return PC_ERR_ARG;
     const std::vector<uint8_t>* s;
     if (slice == -1) s = &c->z_strings[b];
+    else if (c->model == PC_MODEL_WACNN) { if (slice != 0 || b != 0 || c->y_strings.empty()) return PC_ERR_ARG; s = &c->y_strings[0]; }   // one y string per batch
     else if (slice >= 0 && slice < c->res_slices) s = &c->y_strings[(size_t)slice * c->res_B + b];
     else return PC_ERR_ARG;
     *data = s->data(); *len = s->size();
@@ -1805,7 +1869,7 @@ int compress_impl(pc_codec* c, const float* x, int B, int H, int W, const double
 {
     if (!c || !x || !qualities || n_levels < 1 || B <= 0 || H <= 0 || W <= 0 || (H % 64) || (W % 64)) return PC_ERR_ARG;
     if (mask_pol < PC_MASK_POINT_BASED_STD || mask_pol > PC_MASK_THREE_LEVELS_STD) return PC_ERR_ARG;
-    if (!c->finalized || !c->gc.ok() || !c->eb.ok()) return PC_ERR_STATE;
+    if (!c->finalized || !c->gc.ok() || !c->eb.ok() || c->model != PC_MODEL_CHANNEL) return PC_ERR_STATE;
     if (c->eb.n != NCH) return PC_ERR_STATE;
     BusyGuard busy(c);
     if (!busy.ok) return PC_ERR_STATE;
@@ -2007,7 +2071,7 @@ extern "C" int pc_codec_post_filter(pc_codec* c, int which, const float* x, int 
 {
     // net.refine(x) (mode 1, which 0) / net.refine[which](x) (mode 2): unclamped, NCHW [B][3][H][W] in and out (out may be x)
     if (!c || !x || !out || B <= 0 || H <= 0 || W <= 0 || (H % 4) || (W % 4)) return PC_ERR_ARG;
-    if (!c->finalized || !c->post_mode) return PC_ERR_STATE;
+    if (!c->finalized || !c->post_mode || c->model != PC_MODEL_CHANNEL) return PC_ERR_STATE;
     if (which < 0 || which >= c->post_mode) return PC_ERR_ARG;
     BusyGuard busy(c);
     if (!busy.ok) return PC_ERR_STATE;
@@ -2025,7 +2089,7 @@ extern "C" int pc_codec_forward(pc_codec* c, const float* x, int B, int H, int W
 {
     if (!c || !x || !x_hat || !y_lik || !z_lik || B <= 0 || H <= 0 || W <= 0 || (H % 64) || (W % 64)) return PC_ERR_ARG;
     if (mask_pol < PC_MASK_POINT_BASED_STD || mask_pol > PC_MASK_THREE_LEVELS_STD) return PC_ERR_ARG;
-    if (!c->finalized || !c->eb_net) return PC_ERR_STATE;
+    if (!c->finalized || !c->eb_net || c->model != PC_MODEL_CHANNEL) return PC_ERR_STATE;
     BusyGuard busy(c);
     if (!busy.ok) return PC_ERR_STATE;
     HIPCHK(hipSetDevice(c->device));
@@ -2076,7 +2140,7 @@ int decompress_impl(pc_codec* c, const uint8_t* const* y_strings, const size_t* 
 {
     if (!c || !y_strings || !y_lens || !z_strings || !z_lens || !x_hat || !qualities || n_levels < 1 || B <= 0 || zh <= 0 || zw <= 0) return PC_ERR_ARG;
     if (mask_pol < PC_MASK_POINT_BASED_STD || mask_pol > PC_MASK_THREE_LEVELS_STD) return PC_ERR_ARG;
-    if (!c->finalized || !c->gc.ok() || !c->eb.ok() || c->eb.n != NCH) return PC_ERR_STATE;
+    if (!c->finalized || !c->gc.ok() || !c->eb.ok() || c->eb.n != NCH || c->model != PC_MODEL_CHANNEL) return PC_ERR_STATE;
     BusyGuard busy(c);
     if (!busy.ok) return PC_ERR_STATE;
     HIPCHK(hipSetDevice(c->device));
@@ -2192,6 +2256,7 @@ extern "C" int pc_codec_decompress(pc_codec* c, const uint8_t* const* y_strings,
                                    const uint8_t* const* z_strings, const size_t* z_lens, int B, int zh, int zw,
                                    double quality, int mask_pol, float* x_hat, void* stream)
 {
+    if (c && c->model != PC_MODEL_CHANNEL) return PC_ERR_STATE;
     if (n_slices < (quality == 0 ? NS0 : 2 * NS0)) return PC_ERR_ARG;
     return decompress_impl(c, y_strings, y_lens, z_strings, z_lens, B, zh, zw, &quality, 1, mask_pol, x_hat, (hipStream_t)stream);
 }
@@ -2202,6 +2267,7 @@ extern "C" int pc_codec_decompress_packed(pc_codec* c, const uint8_t* data, cons
                                           const double* qualities, int n_levels, int mask_pol, float* x_hat, void* stream)
 {
     if (!c || !data || !lens || B <= 0 || n_levels < 1) return PC_ERR_ARG;
+    if (c->model != PC_MODEL_CHANNEL) return PC_ERR_STATE;
     const size_t ny = (size_t)(NS0 + NS0 * n_levels) * B;
     std::vector<const uint8_t*> ptr(ny + B);
     size_t off = 0;
@@ -2214,6 +2280,171 @@ extern "C" int pc_codec_decompress_levels(pc_codec* c, const uint8_t* const* y_s
                                           const double* qualities, int n_levels, int mask_pol, float* x_hat, void* stream)
 {
     return decompress_impl(c, y_strings, y_lens, z_strings, z_lens, B, zh, zw, qualities, n_levels, mask_pol, x_hat, (hipStream_t)stream);
+}
+
+// ---------------------------------------------------------------------------------------------- WACNN (models/cnn.py:23-340)
+// The single-rate model runs the progressive model's base path: g_a (one 3 -> 320 net), h_a, the EntropyBottleneck, one hyper-synthesis
+// pair and the ten base slices of the chain (chain_params / chain_lrp / prep_encode over steps [0, 10)).  The latent buffers keep their
+// 640-channel pixel stride (chain_setup); WACNN reads and writes their first 320 channels only.  What differs is the framing: every
+// symbol of every slice and image goes into ONE rANS stream (BufferedRansEncoder, :236-270), in the order [slice][B][32][h*w] -- the
+// layout of the chain's symbol / index buffers -- so the encoder codes the whole batch in one call after the last slice, and the decoder
+// continues one stream state from slice to slice (RansDecoder.set_stream / decode_stream, :314-332).
+namespace {
+
+int wacnn_ready(const pc_codec* c)
+{
+    if (!c->finalized || !c->gc.ok() || !c->eb.ok() || c->eb.n != NCH || c->model != PC_MODEL_WACNN) return PC_ERR_STATE;
+    return PC_OK;
+}
+
+}  // namespace
+
+extern "C" int pc_codec_wacnn_compress(pc_codec* c, const float* x, int B, int H, int W, void* stream)
+{
+    if (!c || !x || B <= 0 || H <= 0 || W <= 0 || (H % 64) || (W % 64)) return PC_ERR_ARG;
+    PCCHK(wacnn_ready(c));
+    BusyGuard busy(c);
+    if (!busy.ok) return PC_ERR_STATE;
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = (hipStream_t)stream;
+    CallOrder order(c, st);
+    if (order.rc != PC_OK) return order.rc;
+    g_prof = c->profile ? c : nullptr;
+    g_rowtabs = c->rowtabs;
+    auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+    const double t0 = now();
+    const int h = H / 16, w = W / 16, zh = H / 64, zw = W / 64, ZHW = zh * zw;
+    const size_t M = (size_t)B * h * w;
+    c->last_B = B; c->last_h16 = h; c->last_w16 = w;
+    ChainCtx k;
+    PCCHK(chain_setup(c, CallKind::forward, B, h, w, &k));           // (forward: no custom map / REM checkpoint to consume)
+    float *z, *z_hat;
+    int32_t* z_sym;
+    PCCHK(c->buf("z", (size_t)B * ZHW * NCH, &z));
+    PCCHK(c->buf("z_hat", (size_t)B * ZHW * NCH, &z_hat));
+    PCCHK(c->buf("z_sym", (size_t)B * ZHW * NCH, &z_sym));
+    const size_t n_y = (size_t)NS0 * M * SLICE, n_z = (size_t)B * ZHW * NCH;
+    PCCHK(ensure_host_staging(c, n_y + n_z));
+    c->res_slices = 1; c->res_B = B; c->res_level_coded.clear();
+    c->y_strings.assign(1, {});
+    c->z_strings.assign(B, {});
+
+    PCCHK(g_a(c, st, x, B, H, W, k.y));                                                  // :215
+    PCCHK(h_a(c, st, k.y, B, h, w, z));                                                  // :218
+    PCCHK(pc_eb_quant_launch(z, B, ZHW, NCH, c->medians, z_sym, z_hat, st));             // :219-220
+    PCCHK(hyper(c, st, z_hat, B, zh, zw, 0.0, k.lm, k.ls));                              // :222-223
+    PCCHK(run_chain(k, st, false, nullptr, nullptr));                                    // :237-266
+    HIPCHK(hipMemcpyAsync(c->h_sym, k.sym, n_y * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(c->h_idx, k.idx, n_y * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(c->h_sym + n_y, z_sym, n_z * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    const double th = now();
+    for (size_t e = 0; e < n_z; ++e) c->h_idx[n_y + e] = (int32_t)((e / ZHW) % NCH);      // EntropyBottleneck._build_indexes
+    PCCHK(encode_streams(c, nullptr, nullptr, 0, 0, B, 0, c->h_sym + n_y, c->h_idx + n_y, (size_t)NCH * ZHW));   // z: one string per image
+    std::vector<uint8_t>& ys = c->y_strings[0];                                          // y: one stream for the batch (:268-269)
+    ys.resize(pc_rans_bound(n_y));
+    size_t len = 0;
+    PCCHK(pc_rans_encode_with_indexes(c->h_sym, c->h_idx, n_y, c->gc.cdf.data(), c->gc.n, c->gc.stride, c->gc.len.data(), c->gc.off.data(),
+                                      ys.data(), ys.size(), &len));
+    ys.resize(len);
+    c->t_compress_ms = now() - t0; c->t_host_encode_ms = c->t_host_encode_exposed_ms = now() - th;
+    c->n_sym_encoded = (double)(n_y + n_z);
+    return PC_OK;
+}
+
+extern "C" int pc_codec_wacnn_decompress(pc_codec* c, const uint8_t* y, size_t y_len, const uint8_t* const* z_strings, const size_t* z_lens,
+                                         int B, int zh, int zw, float* x_hat, void* stream)
+{
+    if (!c || !y || !z_strings || !z_lens || !x_hat || B <= 0 || zh <= 0 || zw <= 0) return PC_ERR_ARG;
+    PCCHK(wacnn_ready(c));
+    BusyGuard busy(c);
+    if (!busy.ok) return PC_ERR_STATE;
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = (hipStream_t)stream;
+    CallOrder order(c, st);
+    if (order.rc != PC_OK) return order.rc;
+    g_prof = c->profile ? c : nullptr;
+    g_rowtabs = c->rowtabs;
+    const int h = 4 * zh, w = 4 * zw, HW = h * w, ZHW = zh * zw;
+    c->last_B = B; c->last_h16 = h; c->last_w16 = w;
+    ChainCtx k;
+    PCCHK(chain_setup(c, CallKind::decompress, B, h, w, &k));
+    float* z_hat;
+    int32_t* z_sym;
+    PCCHK(c->buf("z_hat", (size_t)B * ZHW * NCH, &z_hat));
+    PCCHK(c->buf("z_sym", (size_t)B * ZHW * NCH, &z_sym));
+    const size_t per = (size_t)SLICE * HW * B, per_z = (size_t)NCH * ZHW;                // symbols of one slice of the batch / of one z
+    // the previous call's last symbol copy may still read the pinned staging (see decompress_impl)
+    if (c->staging_pending) { HIPCHK(hipEventSynchronize(c->staging_done)); c->staging_pending = false; }
+    if (!c->staging_done) HIPCHK(hipEventCreateWithFlags(&c->staging_done, hipEventDisableTiming));
+    PCCHK(ensure_host_staging(c, std::max(per, per_z * B)));
+    const int nt = c->n_threads == 1 ? 1 : 0;
+    for (size_t e = 0; e < per_z * B; ++e) c->h_idx[e] = (int32_t)((e / ZHW) % NCH);
+    PCCHK(pc_rans_decode_batch(z_strings, z_lens, B, c->h_idx, per_z, c->eb.cdf.data(), c->eb.n, c->eb.stride, c->eb.len.data(),
+                               c->eb.off.data(), c->h_sym, nt));                                                             // :294
+    HIPCHK(hipMemcpyAsync(z_sym, c->h_sym, per_z * B * 4, hipMemcpyHostToDevice, st));
+    PCCHK(pc_eb_dequant_launch(z_sym, B, ZHW, NCH, c->medians, z_hat, st));
+    HIPCHK(hipStreamSynchronize(st));                                                    // h_sym is reused below
+    PCCHK(hyper(c, st, z_hat, B, zh, zw, 0.0, k.lm, k.ls));                              // :295-296
+    // the ten slices on the caller's stream, one host decode of the whole batch's slice in between (a single stream: nothing to split
+    // over lanes or threads, so lanes_dec / host_threads do not apply)
+    uint64_t state[2] = {0, 0};
+    uint8_t* h_idx8 = reinterpret_cast<uint8_t*>(c->h_idx);
+    c->t_host_decode_ms = 0.0;
+    int rc = PC_OK;
+    for (int i = 0; i < NS0 && rc == PC_OK; ++i) {
+        const size_t so = (size_t)i * per;
+        PCCHK(chain_params(k, i, 0, B, st, ""));                                         // :306-314
+        PCCHK(prep_decode_index(k.scale + so, SLICE, nullptr, 0, B, HW, c->scale_table, c->n_table, c->scale_bound, k.idx + so, nullptr, st,
+                                nullptr, 0, k.idx8 + so));                                                                    // :316
+        HIPCHK(hipMemcpyAsync(h_idx8, k.idx8 + so, per, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        const auto td0 = std::chrono::steady_clock::now();
+        rc = pc::rans_decode_u8_stream(y, y_len, state, h_idx8, per, c->gc.dec(), c->h_sym);                              // :318
+        c->t_host_decode_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - td0).count();
+        if (rc != PC_OK) break;
+        HIPCHK(hipMemcpyAsync(k.sym + so, c->h_sym, per * 4, hipMemcpyHostToDevice, st));
+        PCCHK(pc_gc_dequantize(k.sym + so, k.mu + so, SLICE, B, HW, k.yb + 32 * i, D0, st));                               // :320
+        PCCHK(chain_lrp(k, i, 0, B, st, ""));                                                                                // :322-325
+    }
+    if (hipEventRecord(c->staging_done, st) == hipSuccess) c->staging_pending = true;
+    if (rc != PC_OK) return rc;
+    // a stream of another batch size or latent shape, or a damaged one, does not end where its symbols do
+    if (!pc::rans_stream_complete(y_len, state)) return PC_ERR_TRUNCATED;
+    PCCHK(g_s(c, st, c->gs[0], k.yb, B, h, w, x_hat));                                   // :336, clamped
+    c->n_sym_decoded = (double)per_z * B + (double)per * NS0;
+    return PC_OK;
+}
+
+extern "C" int pc_codec_wacnn_forward(pc_codec* c, const float* x, int B, int H, int W, float* x_hat, float* y_lik, float* z_lik, void* stream)
+{
+    if (!c || !x || !x_hat || !y_lik || !z_lik || B <= 0 || H <= 0 || W <= 0 || (H % 64) || (W % 64)) return PC_ERR_ARG;
+    if (!c->finalized || !c->eb_net || c->model != PC_MODEL_WACNN) return PC_ERR_STATE;
+    BusyGuard busy(c);
+    if (!busy.ok) return PC_ERR_STATE;
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = (hipStream_t)stream;
+    CallOrder order(c, st);
+    if (order.rc != PC_OK) return order.rc;
+    g_prof = c->profile ? c : nullptr;
+    g_rowtabs = c->rowtabs;
+    const int h = H / 16, w = W / 16, zh = H / 64, zw = W / 64, ZHW = zh * zw;
+    c->last_B = B; c->last_h16 = h; c->last_w16 = w;
+    ChainCtx k;
+    PCCHK(chain_setup(c, CallKind::forward, B, h, w, &k));
+    float *z, *z_hat;
+    int32_t* z_sym;
+    PCCHK(c->buf("z", (size_t)B * ZHW * NCH, &z));
+    PCCHK(c->buf("z_hat", (size_t)B * ZHW * NCH, &z_hat));
+    PCCHK(c->buf("z_sym", (size_t)B * ZHW * NCH, &z_sym));
+    k.lik = y_lik; k.lik_nch = D0;
+    PCCHK(g_a(c, st, x, B, H, W, k.y));                                                  // :146
+    PCCHK(h_a(c, st, k.y, B, h, w, z));                                                  // :148
+    PCCHK(pc_eb_quant_launch(z, B, ZHW, NCH, c->medians, z_sym, z_hat, st));             // :154-156 (round about the medians)
+    PCCHK(pc_eb_likelihood_launch(z_sym, B, ZHW, NCH, c->medians, c->eb_net, z_lik, st));   // :149
+    PCCHK(hyper(c, st, z_hat, B, zh, zw, 0.0, k.lm, k.ls));                              // :158-159
+    PCCHK(run_chain(k, st, false, nullptr, nullptr));                                    // :165-185
+    return g_s(c, st, c->gs[0], k.yb, B, h, w, x_hat, PC_EPI_NONE);                      // :187, unclamped
 }
 
 extern "C" int pc_codec_read_tap(pc_codec* c, const char* name, float* host_out, size_t cap, size_t* n)

@@ -483,6 +483,32 @@ int rans_decode_u8_batch(const uint8_t* const* encoded, const size_t* encoded_le
     return rc;
 }
 
+int rans_decode_u8_stream(const uint8_t* encoded, size_t encoded_len, uint64_t* state, const uint8_t* indexes, size_t n, const DecTables& t,
+                          int32_t* out)
+{
+    if (!encoded || !state || (!indexes && n) || !t.cdf || !t.lut || (!out && n)) return PC_ERR_ARG;
+    DecState A;
+    A.init(encoded, encoded_len);
+    if (A.err) return A.err;
+    if (state[1] != 0) {                                                  // continue where the previous call stopped
+        if (state[1] < 2 || state[1] > A.nw) return PC_ERR_ARG;
+        A.x = state[0]; A.p = (size_t)state[1];
+    }
+    for (size_t i = 0; i < n; ++i) {
+        const int ci = indexes[i];
+        if (ci >= t.n) return PC_ERR_INDEX;
+        out[i] = A.symbol(ci, t);
+        if (A.err) return A.err;
+    }
+    state[0] = A.x; state[1] = A.p;
+    return PC_OK;
+}
+
+bool rans_stream_complete(size_t encoded_len, const uint64_t* state)
+{
+    return encoded_len % 4 == 0 && state[1] == encoded_len / 4 && state[0] == kRansL;
+}
+
 }  // namespace pc
 
 extern "C" int pc_rans_encode_batch(const int32_t* symbols, const int32_t* indexes, size_t n_streams, size_t n,

@@ -29,5 +29,12 @@ struct DecTables {
 void build_decode_lut(const int32_t* cdf, int n, int stride, const int32_t* len, uint64_t* lut);
 int rans_decode_u8_batch(const uint8_t* const* encoded, const size_t* encoded_lens, size_t n_streams, const uint8_t* indexes, size_t n,
                          const DecTables& t, int32_t* out, int n_threads);
+// The same fast decoder over ONE stream decoded in several calls (WACNN's per-batch y string: RansDecoder.set_stream + one decode_stream
+// per slice, models/cnn.py:314,332).  state[0] = rANS state, state[1] = next 32-bit word; zero both before the first call.  Same symbols
+// and error codes as pc_rans_decode_stream.
+int rans_decode_u8_stream(const uint8_t* encoded, size_t encoded_len, uint64_t* state, const uint8_t* indexes, size_t n, const DecTables& t,
+                          int32_t* out);
+// after the last call: the stream was consumed exactly (every word read, the state back at the encoder's initial value)
+bool rans_stream_complete(size_t encoded_len, const uint64_t* state);
 }  // namespace pc
 #endif

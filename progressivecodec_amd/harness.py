@@ -300,3 +300,33 @@ def estimate_rd(model, images, pr_list=None, mask_pol="point-based-std", device=
     n_img = max(1, len(rows) // max(1, len(pr_list)))
     avg = lambda key, p: sum(r[key] for r in rows if r["quality"] == p) / n_img
     return [avg("bpp", p) for p in pr_list], [avg("psnr", p) for p in pr_list], rows
+
+
+def compress_single_rate(models, images, device="cuda", ms_ssim=False):
+    """The "base" anchor curve of the paper (train.py:379-380): the single-rate WACNN at one checkpoint per rate point.  For every model
+    of `models` (progressivecodec_amd.WACNN, loaded and updated), every image is coded as compress_with_ac codes one level: centre pad to
+    a multiple of 64, compress -> decompress, un-pad and clamp, PSNR, bpp = 8 * (y string + z string bytes) / (H*W) over the unpadded
+    size; ms_ssim=True adds the MS-SSIM column (metrics.ms_ssim, data_range=1).  Returns one (bpp, psnr[, ms_ssim]) row per model,
+    averaged over the images."""
+    import torch
+    import torch.nn.functional as F
+    imgs = [(x if x.dim() == 4 else x.unsqueeze(0)) for x in images]
+    out = []
+    with torch.no_grad():
+        for model in models:
+            acc = [0.0, 0.0, 0.0]
+            for x in imgs:
+                x = x.to(device)
+                h, w = x.shape[2:]
+                pad, unpad = compute_padding(h, w, 64)
+                data = model.compress(F.pad(x, pad, mode="constant", value=0))
+                x_hat = F.pad(model.decompress(data["strings"], data["shape"])["x_hat"], unpad).clamp_(0, 1)
+                y_strings, z_strings = data["strings"]
+                acc[0] += 8.0 * (sum(len(s) for s in y_strings) + sum(len(s) for s in z_strings)) / (h * w)
+                mse = torch.mean((x - x_hat) ** 2).item()
+                acc[1] += -10.0 * math.log10(mse) if mse > 0 else float("inf")
+                if ms_ssim:
+                    acc[2] += _ms_ssim_of(x, x_hat)[0]
+            n = max(1, len(imgs))
+            out.append((acc[0] / n, acc[1] / n, acc[2] / n) if ms_ssim else (acc[0] / n, acc[1] / n))
+    return out

@@ -46,24 +46,13 @@ def _one_call_at_a_time(fn):
     return wrapper
 
 
-class ChannelProgresssiveWACNN(_module_base()):
-    """A ``torch.nn.Module`` (isinstance checks, ``state_dict()``, ``parameters()``, ``eval()`` ... behave as the caller of the reference
-    expects: SURVEY.md section 8b) whose tensors are host-side copies of what was loaded -- the working weights live packed in
-    HBM inside the native codec object."""
+class _NativeCodecModule(_module_base()):
+    """The ``torch.nn.Module`` surface shared by the models here (ChannelProgresssiveWACNN and WACNN): a native codec object holds the
+    working weights packed in HBM, the module keeps host copies of what was loaded (state_dict, parameters, buffers), builds the entropy
+    tables in update() and serialises calls into the object.  Subclasses give the state-dict layout (_spec) and configure the native
+    object before it is finalised (_configure_native)."""
 
-    def __init__(self, N=192, M=640, division_dimension=(320, 640), dim_chunk=32, multiple_decoder=True,
-                 multiple_encoder=False, multiple_hyperprior=True, mask_policy="two-levels", lmbda_list=(0.0055, 0.04),
-                 joiner_policy="res", support_progressive_slices=5, delta_encode=True, u_net_post=0, device="cuda:0", **kwargs):
-        super().__init__()
-        self.cfg = CodecConfig(N=N, M=M, division_dimension=tuple(division_dimension), dim_chunk=dim_chunk,
-                               multiple_decoder=multiple_decoder, multiple_encoder=multiple_encoder,
-                               multiple_hyperprior=multiple_hyperprior, delta_encode=delta_encode,
-                               joiner_policy=joiner_policy, support_progressive_slices=support_progressive_slices,
-                               mask_policy=mask_policy, u_net_post=u_net_post)
-        self.cfg.check_supported()
-        self.u_net_post = u_net_post
-        self.mask_policy = mask_policy
-        self.lmbda_list = list(lmbda_list)
+    def _open(self, device):
         import torch
         self.device = torch.device(device)
         if self.device.type != "cuda":
@@ -77,6 +66,12 @@ class ChannelProgresssiveWACNN(_module_base()):
         self._scale_table = None
         self._finalized = False
 
+    def _spec(self):
+        raise NotImplementedError
+
+    def _configure_native(self):
+        pass
+
     def __del__(self):
         h = self.__dict__.get("_h", None)
         if h is not None and h.value:
@@ -89,11 +84,9 @@ class ChannelProgresssiveWACNN(_module_base()):
         compress()/decompress() path)."""
         return self
 
-    def forward(self, *args, **kwargs):
-        raise NotImplementedError("training forward() (CHProg_cnn.py:478-682) is out of scope; use forward_single_quality() for rate estimation")
-
     def state_dict(self, *args, destination=None, prefix="", keep_vars=False):
-        """The reference's 1019-key layout (models/cnn.py:195-202), as loaded, with the CDF buffers update() built."""
+        """The reference's state-dict layout (models/cnn.py:195-202; 1019 keys for ChannelProgresssiveWACNN, 585 for WACNN), as loaded, with
+        the CDF buffers update() built."""
         import torch
         out = OrderedDict() if destination is None else destination
         if self._sd is None:
@@ -113,7 +106,7 @@ class ChannelProgresssiveWACNN(_module_base()):
         import torch
         if self._sd is None:
             return
-        spec = param_spec(self.cfg)
+        spec = self._spec()
         for k, a in self._sd.items():
             if spec[k][2] in _PARAM_KINDS:
                 yield prefix + k, torch.nn.Parameter(torch.from_numpy(np.array(a, copy=True)), requires_grad=False)
@@ -150,7 +143,7 @@ class ChannelProgresssiveWACNN(_module_base()):
             a = np.ascontiguousarray(a, np.float32)
             shp = (C.c_int64 * a.ndim)(*a.shape)
             check(lib().pc_codec_set_tensor(self._h, k.encode(), a.ctypes.data_as(C.c_void_p), _DT["float32"], shp, a.ndim), f"set_tensor({k})")
-        spec = param_spec(self.cfg)
+        spec = self._spec()
         missing = [k for k in spec if k not in state_dict]
         unexpected = [k for k in state_dict if k not in spec]
         if strict and (missing or unexpected):
@@ -171,7 +164,7 @@ class ChannelProgresssiveWACNN(_module_base()):
             check(lib().pc_codec_set_tensor(self._h, k.encode(), a.ctypes.data_as(C.c_void_p), _DT[dtype], shp, a.ndim),
                   f"set_tensor({k})")
         self._sd = sd
-        check(lib().pc_codec_set_post_filter(self._h, self.cfg.u_net_post), "pc_codec_set_post_filter")
+        self._configure_native()
         check(lib().pc_codec_finalize(self._h), "pc_codec_finalize")
         self._finalized = True
         for which, p in ((0, "gaussian_conditional"), (1, "entropy_bottleneck")):
@@ -210,26 +203,6 @@ class ChannelProgresssiveWACNN(_module_base()):
             updated = True
         return updated
 
-    def post_filter(self, x, which=None):
-        """``net.refine(x)`` (u_net_post=1) or ``net.refine[which](x)`` (u_net_post=2; default which=1, the net every decode path uses):
-        the UNet post-filter alone, unclamped, on a [B, 3, H, W] device tensor with H and W multiples of 4 (CHProg_cnn.py:277-284)."""
-        import torch
-        if not self.cfg.u_net_post:
-            raise RuntimeError("this model has no post-filter (u_net_post=0)")
-        if not self._finalized:
-            raise ValueError("load_state_dict() first")
-        if which is None:
-            which = 1 if self.cfg.u_net_post == 2 else 0
-        if x.dim() != 4 or x.shape[1] != 3:
-            raise ValueError(f"post_filter expects a [B, 3, H, W] tensor, got {tuple(x.shape)}")
-        xi = x.to(self.device, torch.float32).contiguous()
-        out = torch.empty_like(xi)
-        B, _, H, W = xi.shape
-        with self._call_lock:
-            check(lib().pc_codec_post_filter(self._h, int(which), C.c_void_p(xi.data_ptr()), B, H, W, C.c_void_p(out.data_ptr()), self._stream()),
-                  "pc_codec_post_filter")
-        return out
-
     def set_option(self, name, value):
         """pc_codec_set_option: schedule options of this object ("serial_schedule", "lanes_enc", "lanes_dec", "host_threads") -- results never
         depend on them.  Options belong to the native handle: a reload of a finalised codec (load_state_dict) starts from the defaults."""
@@ -253,6 +226,64 @@ class ChannelProgresssiveWACNN(_module_base()):
         for k in lens:
             out.append(raw[off:off + k])
             off += k
+        return out
+
+    def read_tap(self, name, dtype=np.float32):
+        n = C.c_size_t()
+        f = lib().pc_codec_read_tap
+        check(f(self._h, name.encode(), None, 0, C.byref(n)), "read_tap")
+        out = np.empty(n.value, dtype)
+        check(f(self._h, name.encode(), out.ctypes.data_as(C.c_void_p), n.value, C.byref(n)), "read_tap")
+        return out
+
+
+class ChannelProgresssiveWACNN(_NativeCodecModule):
+    """A ``torch.nn.Module`` (isinstance checks, ``state_dict()``, ``parameters()``, ``eval()`` ... behave as the caller of the reference
+    expects: SURVEY.md section 8b) whose tensors are host-side copies of what was loaded -- the working weights live packed in
+    HBM inside the native codec object."""
+
+    def __init__(self, N=192, M=640, division_dimension=(320, 640), dim_chunk=32, multiple_decoder=True,
+                 multiple_encoder=False, multiple_hyperprior=True, mask_policy="two-levels", lmbda_list=(0.0055, 0.04),
+                 joiner_policy="res", support_progressive_slices=5, delta_encode=True, u_net_post=0, device="cuda:0", **kwargs):
+        super().__init__()
+        self.cfg = CodecConfig(N=N, M=M, division_dimension=tuple(division_dimension), dim_chunk=dim_chunk,
+                               multiple_decoder=multiple_decoder, multiple_encoder=multiple_encoder,
+                               multiple_hyperprior=multiple_hyperprior, delta_encode=delta_encode,
+                               joiner_policy=joiner_policy, support_progressive_slices=support_progressive_slices,
+                               mask_policy=mask_policy, u_net_post=u_net_post)
+        self.cfg.check_supported()
+        self.u_net_post = u_net_post
+        self.mask_policy = mask_policy
+        self.lmbda_list = list(lmbda_list)
+        self._open(device)
+
+    def _spec(self):
+        return param_spec(self.cfg)
+
+    def _configure_native(self):
+        check(lib().pc_codec_set_post_filter(self._h, self.cfg.u_net_post), "pc_codec_set_post_filter")
+
+    def forward(self, *args, **kwargs):
+        raise NotImplementedError("training forward() (CHProg_cnn.py:478-682) is out of scope; use forward_single_quality() for rate estimation")
+
+    def post_filter(self, x, which=None):
+        """``net.refine(x)`` (u_net_post=1) or ``net.refine[which](x)`` (u_net_post=2; default which=1, the net every decode path uses):
+        the UNet post-filter alone, unclamped, on a [B, 3, H, W] device tensor with H and W multiples of 4 (CHProg_cnn.py:277-284)."""
+        import torch
+        if not self.cfg.u_net_post:
+            raise RuntimeError("this model has no post-filter (u_net_post=0)")
+        if not self._finalized:
+            raise ValueError("load_state_dict() first")
+        if which is None:
+            which = 1 if self.cfg.u_net_post == 2 else 0
+        if x.dim() != 4 or x.shape[1] != 3:
+            raise ValueError(f"post_filter expects a [B, 3, H, W] tensor, got {tuple(x.shape)}")
+        xi = x.to(self.device, torch.float32).contiguous()
+        out = torch.empty_like(xi)
+        B, _, H, W = xi.shape
+        with self._call_lock:
+            check(lib().pc_codec_post_filter(self._h, int(which), C.c_void_p(xi.data_ptr()), B, H, W, C.c_void_p(out.data_ptr()), self._stream()),
+                  "pc_codec_post_filter")
         return out
 
     def _decompress_packed(self, slots, z_strings, B, zh, zw, qualities, mask_pol):
@@ -457,10 +488,3 @@ class ChannelProgresssiveWACNN(_module_base()):
         return torch.from_numpy(np.ascontiguousarray(a.transpose(0, 3, 1, 2)))
 
     # ------------------------------------------------------------------ test taps
-    def read_tap(self, name, dtype=np.float32):
-        n = C.c_size_t()
-        f = lib().pc_codec_read_tap
-        check(f(self._h, name.encode(), None, 0, C.byref(n)), "read_tap")
-        out = np.empty(n.value, dtype)
-        check(f(self._h, name.encode(), out.ctypes.data_as(C.c_void_p), n.value, C.byref(n)), "read_tap")
-        return out

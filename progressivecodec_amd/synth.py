@@ -53,8 +53,9 @@ def scale_table(cfg: CodecConfig = CodecConfig()) -> np.ndarray:
                                     cfg.scales_levels)).numpy().copy()
 
 
-def synthetic_state_dict(cfg: CodecConfig = CodecConfig(), seed: int = 0, as_torch: bool = True):
-    spec = param_spec(cfg)
+def synthetic_state_dict(cfg: CodecConfig = CodecConfig(), seed: int = 0, as_torch: bool = True, spec=None):
+    """spec: another state-dict layout drawn with the same per-kind recipe (synthetic_wacnn_state_dict); default param_spec(cfg)"""
+    spec = param_spec(cfg) if spec is None else spec
     out = OrderedDict()
     eb_scale = 10.0 ** (1.0 / 5.0)  # entropy_models.py:325 (init_scale=10, 4 filters)
     filters = (1, 3, 3, 3, 3, 1)
@@ -86,7 +87,7 @@ def synthetic_state_dict(cfg: CodecConfig = CodecConfig(), seed: int = 0, as_tor
             v = g.standard_normal(shape) * 0.05
             if name.endswith(".8.bias") and name.startswith("cc_scale_transforms"):
                 v = v + BIAS_S
-            if name == "g_s.0.8.bias" or name == "g_s.1.8.bias":
+            if name in ("g_s.0.8.bias", "g_s.1.8.bias", "g_s.8.bias"):
                 v = v + 0.45
         elif kind == "gdn_beta":
             beta = 1.0 + 0.5 * g.random(shape)
@@ -147,6 +148,14 @@ def synthetic_state_dict(cfg: CodecConfig = CodecConfig(), seed: int = 0, as_tor
         import torch
         return OrderedDict((k, torch.from_numpy(v)) for k, v in out.items())
     return out
+
+
+def synthetic_wacnn_state_dict(seed: int = 0, as_torch: bool = True):
+    """Deterministic weights in the reference WACNN(192, 320) layout (arch.wacnn_param_spec), drawn with the recipe above: its layers
+    are the progressive model's base path, so the same amplification (g_a.7 x AMP_Y, cc_scale_transforms.*.8 x AMP_S + BIAS_S, h_a.8,
+    h_*_s.8) spreads the scale indices and gives the strings real content (tests/golden/wacnn.json records the index histogram)."""
+    from .arch import wacnn_param_spec
+    return synthetic_state_dict(seed=seed, as_torch=as_torch, spec=wacnn_param_spec())
 
 
 def synthetic_post_state_dict(check_multiple: int = 3, dimension: str = "big", seed: int = 0, as_torch: bool = True, mu_std: bool = False):
