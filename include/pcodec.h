@@ -116,6 +116,8 @@ PC_API int pc_pmf_to_quantized_cdf(const float* pmf, int n, int precision, uint3
 /* Generic convolution / transposed convolution / linear layer with the reference's weight layout.
  *   kind 0: nn.Conv2d weight [Cout][Cin][k][k], stride s, padding k/2   (models/utils.py:186, layers/layers.py:15,27)
  *   kind 1: nn.ConvTranspose2d(k=5, s=2, p=2, output_padding=1) weight [Cin][Cout][5][5]   (models/utils.py:196)
+ *   kind 2 (pc_pack_conv_weight only): the same transposed conv with Cout = 3, k = 5 and Cin % 16 == 0 rewritten as the codec's sub-pixel
+ *           output layer -- a 3x3 stride-1 conv with 12 channels n = c*4 + py*2 + px, PixelShuffle(2) in the store; 9 * 12 * Cin floats
  * `w_packed` must come from pc_pack_conv_weight (tap-major; the layout -- [taps][Cin][Cout] or [taps][Cout][Cin] -- is a
  * function of (kind, Cin, Cout, k) only).
  * act: 0 none, 1 GELU.  x: [B][H][W][Cin], out: [B][Ho][Wo][Cout]. */
@@ -329,6 +331,60 @@ PC_API int pc_codec_host_stats(const pc_codec* c, double* out, int n);
  * compares that form with the contract's scalar pc_geluf (include/pc_math.h) over ALL 2^32 float arguments on the current device.
  * *n_mismatch must be 0; *n_nan_payload counts arguments for which both forms return NaN with different payload bits.  Synchronous. */
 PC_API int pc_selftest_packed_gelu(uint64_t* n_mismatch, uint64_t* n_nan_payload);
+
+/* Test aid: one launch of the conv launcher (every kernel, epilogue, operand and output form the codec uses) from a plain descriptor.
+ * The launch parameters are built with the codec's own tap tables (conv k x k / transposed conv 5 s2 / the 192 -> 3 sub-pixel output layer)
+ * and go through the same launcher as every codec layer.  Weights come from pc_pack_conv_weight with the same kind (kind 2: the sub-pixel
+ * weights; its bias has 12 entries, bias[n] = b[n >> 2]).  Pointers are device pointers; asynchronous on `stream`.
+ *   plan (optional, 2 ints): [0] the kernel instantiation the launcher chose (PC_PLAN_*), [1] the epilogue form (PC_FORM_*).
+ * Returns PC_ERR_ARG for every launch the launcher refuses (nothing is written then). */
+#define PC_TEST_MAX_SEG 8
+typedef struct pc_test_conv_desc {
+    /* input: nseg NHWC segments (channel axis = their concatenation), or smallc = 1: one input `seg_ptr[0]` of Cin channels, element
+     * (b, y, x, c) at b * in_sb + y * in_sy + x * in_sx + c * in_sc */
+    int nseg;
+    const float* seg_ptr[PC_TEST_MAX_SEG];
+    int seg_ld[PC_TEST_MAX_SEG];
+    int seg_nch[PC_TEST_MAX_SEG];
+    int smallc;
+    int64_t in_sb, in_sy, in_sx, in_sc;
+    int Cin, B, H, W;
+    /* geometry: kind 0 conv k x k (padding k / 2) with `stride`, 1 ConvTranspose2d(5, s2, p2, op1), 2 the sub-pixel output layer */
+    int kind, k, stride;
+    int square;                            /* contract over x^2 (GDN / IGDN) */
+    const float* w; const float* bias; int Cout;   /* Cout of the packed weights (kind 2: 12) */
+    int epi;                               /* PC_EPI_* (progressivecodec_amd/csrc/pc_device.h) */
+    const float* aux0; int ld0;
+    const float* aux1; int ld1;
+    const float* fg_gamma; const float* fg_beta;   /* fused input-layer GDN (3 -> 192) */
+    float* out;
+    int64_t out_sb, out_sy, out_sx, out_sc;
+    int pixel_shuffle;
+    float* out_relu;
+    int ngroup;                            /* 2: a second GEMM on g1_seg0 / g1_w / g1_bias -> g1_out */
+    const float* g1_seg0; const float* g1_w; const float* g1_bias; float* g1_out;
+    int tile_cfg;                          /* PC_TILE_* of the layout-0 kernel (0: automatic) */
+} pc_test_conv_desc;
+#define PC_PLAN_UNI_16_3 1                 /* conv_igemm_uni_kernel<BK 16, 3 stages>: grids above 256 64x64 blocks */
+#define PC_PLAN_UNI_32_2 2                 /* <BK 32, 2 stages>: small grids, K <= 256 per phase */
+#define PC_PLAN_UNI_32_3 3                 /* <BK 32, 3 stages>: small grids */
+#define PC_PLAN_UNI_32_2_SQ 4              /* <BK 32, 2 stages, x^2 operand>: GDN / IGDN */
+#define PC_PLAN_UNI_OTHER 5                /* a tuning-only instantiation */
+#define PC_PLAN_L0_64x64 6                 /* conv_igemm_kernel (weight layout 0) */
+#define PC_PLAN_L0_64x64_SMALLC 7
+#define PC_PLAN_L0_128x32 8
+#define PC_PLAN_L0_128x32_SMALLC 9
+#define PC_PLAN_L0_128x128 10
+#define PC_PLAN_L0_128x128_SMALLC 11
+#define PC_PLAN_IN_GDN 12                  /* conv_igemm_in_gdn_kernel */
+#define PC_FORM_SLOW 1                     /* unified kernel: generic epilogue (any strides, aux read from global) */
+#define PC_FORM_DIRECT 2                   /* unified kernel: dense output, rows in pixel order */
+#define PC_FORM_TABLE 3                    /* unified kernel: LDS row table (permuted rows, strided output, PixelShuffle) */
+#define PC_FORM_NCHW_PS 4                  /* unified kernel: NCHW PixelShuffle through LDS */
+#define PC_FORM_L0_DIRECT 5                /* layout-0 kernel: dense output without aux tensors */
+#define PC_FORM_L0_GENERIC 6               /* layout-0 kernel: generic epilogue */
+#define PC_FORM_IN_GDN 7                   /* fused input-layer GDN */
+PC_API int pc_test_conv(const pc_test_conv_desc* d, int* plan, void* stream);
 
 /* Debug/test taps: copy an internal device tensor of the last call to host ("y", "z", "latent_means", ...). */
 PC_API int pc_codec_read_tap(pc_codec* c, const char* name, float* host_out, size_t cap_floats, size_t* n_floats);

@@ -245,22 +245,27 @@ int load_conv(pc_codec* c, const std::string& p, int Cin, int Cout, int k, int k
 // dy = +1,0,-1 (outer), dx = +1,0,-1 (inner), so for every phase the taps it really has appear in ascending (ky,kx) -- the
 // contract's order for a transposed-conv phase -- and a zero-weight tap leaves the fmaf chain's value unchanged: bit-identical
 // to the four-phase form (tests/test_gpu_codec.py vs the oracle's four-phase restatement).
-int load_deconv3_subpixel(pc_codec* c, const std::string& p, int Cin, ConvW* out)
+void pack_deconv3_subpixel(const float* W, int Cin, float* packed)   // W [Cin][3][5][5] -> layout 1 [9 taps][12][Cin]
 {
-    const HostTensor* w = find(c, p + ".weight", PC_F32, {Cin, 3, 5, 5});
-    const HostTensor* b = find(c, p + ".bias", PC_F32, {3});
-    if (!w || !b || Cin % 16) { std::fprintf(stderr, "[pcodec] missing/mis-shaped tensor %s\n", p.c_str()); return PC_ERR_MISSING; }
-    const float* W = reinterpret_cast<const float*>(w->data.data());
-    std::vector<float> packed((size_t)9 * 12 * Cin, 0.0f);                    // layout 1: [tap][n][ci]
     for (int t = 0; t < 9; ++t) {
         const int dy = 1 - t / 3, dx = 1 - t % 3;
         for (int n = 0; n < 12; ++n) {
             const int cch = n >> 2, py = (n >> 1) & 1, px = n & 1;
             const int ky = py + 2 - 2 * dy, kx = px + 2 - 2 * dx;
-            if (ky < 0 || ky >= 5 || kx < 0 || kx >= 5) continue;
-            for (int ci = 0; ci < Cin; ++ci) packed[((size_t)t * 12 + n) * Cin + ci] = W[(((size_t)ci * 3 + cch) * 5 + ky) * 5 + kx];
+            float* dst = packed + ((size_t)t * 12 + n) * Cin;
+            for (int ci = 0; ci < Cin; ++ci)
+                dst[ci] = (ky < 0 || ky >= 5 || kx < 0 || kx >= 5) ? 0.0f : W[(((size_t)ci * 3 + cch) * 5 + ky) * 5 + kx];
         }
     }
+}
+
+int load_deconv3_subpixel(pc_codec* c, const std::string& p, int Cin, ConvW* out)
+{
+    const HostTensor* w = find(c, p + ".weight", PC_F32, {Cin, 3, 5, 5});
+    const HostTensor* b = find(c, p + ".bias", PC_F32, {3});
+    if (!w || !b || Cin % 16) { std::fprintf(stderr, "[pcodec] missing/mis-shaped tensor %s\n", p.c_str()); return PC_ERR_MISSING; }
+    std::vector<float> packed((size_t)9 * 12 * Cin);                          // layout 1: [tap][n][ci]
+    pack_deconv3_subpixel(reinterpret_cast<const float*>(w->data.data()), Cin, packed.data());
     PCCHK(upload(c, packed, &out->w));
     std::vector<float> bias(12);
     for (int n = 0; n < 12; ++n) bias[n] = reinterpret_cast<const float*>(b->data.data())[n >> 2];
@@ -416,6 +421,13 @@ void fill_conv_taps(pc_conv_params& q, int k, int stride)
             q.dy[0][t] = (ky - pad); q.dx[0][t] = (kx - pad); q.wtap[0][t] = t;
         }
     q.osy = q.osx = 1; q.ooy[0] = q.oox[0] = 0;
+}
+
+// the 3x3 stride-1 tap list of the sub-pixel output layer (pack_deconv3_subpixel): tap t = (dy, dx) = (1 - t / 3, 1 - t % 3)
+void fill_subpixel_taps(pc_conv_params& q)
+{
+    q.nphase = 1; q.ntap[0] = 9; q.stride = 1; q.osy = q.osx = 1; q.ooy[0] = q.oox[0] = 0;
+    for (int t = 0; t < 9; ++t) { q.dy[0][t] = 1 - t / 3; q.dx[0][t] = 1 - t % 3; q.wtap[0][t] = t; }
 }
 
 void fill_deconv_taps(pc_conv_params& q)   // ConvTranspose2d(5, s2, p2, op1) as 4 output phases
@@ -650,8 +662,7 @@ int g_s(pc_codec* c, hipStream_t st, const GsW& g, const float* yhat, int B, int
         const int H = 8 * h, W = 8 * w;
         q.nseg = 1; q.seg[0].ptr = t1; q.seg[0].ld = NCH; q.seg[0].nch = NCH; q.Cin = NCH;
         q.B = B; q.H = H; q.W = W;
-        q.nphase = 1; q.ntap[0] = 9; q.stride = 1; q.osy = q.osx = 1;
-        for (int t = 0; t < 9; ++t) { q.dy[0][t] = 1 - t / 3; q.dx[0][t] = 1 - t % 3; q.wtap[0][t] = t; }
+        fill_subpixel_taps(q);
         q.w = g.d8.w; q.wlayout = 1; q.bias = g.d8.b; q.Cout = 12;
         q.Ho = H; q.Wo = W; q.outH = 2 * H; q.outW = 2 * W; q.M = B * H * W;
         q.pixel_shuffle = 1;
@@ -838,6 +849,12 @@ int hyper(pc_codec* c, hipStream_t st, const float* z_hat, int B, int zh, int zw
 extern "C" int pc_pack_conv_weight(const float* w, int kind, int Cout, int Cin, int k, float* out)
 {
     if (!w || !out || Cout <= 0 || Cin <= 0 || k <= 0) return PC_ERR_ARG;
+    if (kind == 2) {                                   // the sub-pixel output layer (load_deconv3_subpixel)
+        if (Cout != 3 || k != 5 || Cin % 16) return PC_ERR_ARG;
+        pack_deconv3_subpixel(w, Cin, out);
+        return PC_OK;
+    }
+    if (kind != 0 && kind != 1) return PC_ERR_ARG;
     auto src = [&](int co, int ci, int ky, int kx) -> float {
         return kind == 0 ? w[(((size_t)co * Cin + ci) * k + ky) * k + kx] : w[(((size_t)ci * Cout + co) * k + ky) * k + kx];
     };
@@ -883,6 +900,47 @@ extern "C" int pc_conv2d_nhwc(const float* x, int B, int H, int W, int Cin, cons
     q.M = B * q.Ho * q.Wo;
     q.out = out; q.out_sc = 1; q.out_sx = Cout; q.out_sy = (int64_t)q.outW * Cout; q.out_sb = (int64_t)q.outH * q.outW * Cout;
     return pc_conv_launch(q, (hipStream_t)stream);
+}
+
+// Test aid (include/pcodec.h): the descriptor -> pc_conv_params with the codec's own tap tables, then the launcher
+extern "C" int pc_test_conv(const pc_test_conv_desc* d, int* plan, void* stream)
+{
+    if (plan) plan[0] = plan[1] = 0;
+    if (!d || !d->out || !d->w || d->nseg < 1 || d->nseg > PC_MAX_SEG || d->B <= 0 || d->H <= 0 || d->W <= 0) return PC_ERR_ARG;
+    pc_conv_params q;
+    std::memset(&q, 0, sizeof(q));
+    q.nseg = d->nseg;
+    for (int s = 0; s < d->nseg; ++s) { q.seg[s].ptr = d->seg_ptr[s]; q.seg[s].ld = d->seg_ld[s]; q.seg[s].nch = d->seg_nch[s]; }
+    q.smallc = d->smallc ? 1 : 0;
+    q.in_sb = d->in_sb; q.in_sy = d->in_sy; q.in_sx = d->in_sx; q.in_sc = d->in_sc;
+    q.Cin = d->Cin; q.B = d->B; q.H = d->H; q.W = d->W;
+    q.square = d->square ? 1 : 0;
+    q.w = d->w; q.bias = d->bias; q.Cout = d->Cout; q.tile_cfg = d->tile_cfg;
+    q.epi = d->epi; q.aux0 = d->aux0; q.ld0 = d->ld0; q.aux1 = d->aux1; q.ld1 = d->ld1;
+    q.fg_gamma = d->fg_gamma; q.fg_beta = d->fg_beta;
+    if (d->kind == 0) {
+        if (d->k <= 0 || d->k > 5 || d->stride <= 0) return PC_ERR_ARG;
+        fill_conv_taps(q, d->k, d->stride);
+        q.Ho = (d->H + 2 * (d->k / 2) - d->k) / d->stride + 1; q.Wo = (d->W + 2 * (d->k / 2) - d->k) / d->stride + 1;
+        q.outH = q.Ho; q.outW = q.Wo;
+        q.wlayout = q.square ? 1 : pc_conv_weight_layout(0, d->Cin, d->Cout, d->k);
+    } else if (d->kind == 1) {
+        fill_deconv_taps(q);
+        q.Ho = d->H; q.Wo = d->W; q.outH = 2 * d->H; q.outW = 2 * d->W;
+        q.wlayout = pc_conv_weight_layout(1, d->Cin, d->Cout, 5);
+    } else if (d->kind == 2) {
+        if (d->Cout != 12) return PC_ERR_ARG;
+        fill_subpixel_taps(q);
+        q.Ho = d->H; q.Wo = d->W; q.outH = d->H; q.outW = d->W;
+        q.wlayout = 1;
+    } else return PC_ERR_ARG;
+    q.M = d->B * q.Ho * q.Wo;
+    q.pixel_shuffle = (d->pixel_shuffle || d->kind == 2) ? 1 : 0;
+    if (q.pixel_shuffle) { q.outH *= 2; q.outW *= 2; }
+    q.out = d->out; q.out_sb = d->out_sb; q.out_sy = d->out_sy; q.out_sx = d->out_sx; q.out_sc = d->out_sc;
+    q.out_relu = d->out_relu;
+    if (d->ngroup == 2) { q.ngroup = 2; q.g1_seg0 = d->g1_seg0; q.g1_w = d->g1_w; q.g1_bias = d->g1_bias; q.g1_out = d->g1_out; }
+    return pc_conv_launch(q, (hipStream_t)stream, plan);
 }
 
 extern "C" int pc_gdn_nhwc(const float* x, int B, int H, int W, int C, const float* beta, const float* gamma, int inverse,

@@ -1604,7 +1604,7 @@ void conv_rowtab_unpin(const pc_conv_params& p)
 }
 
 template <int BK, int S, int TM, int TN, bool SQ = false, int DBG = 0>
-hipError_t launch_uni(const pc_conv_params& p, hipStream_t stream)
+hipError_t launch_uni(const pc_conv_params& p, hipStream_t stream, int* plan)
 {
     constexpr int BM = 64 * TM, BN = 64 * TN;
     int tmax = 0;
@@ -1613,6 +1613,20 @@ hipError_t launch_uni(const pc_conv_params& p, hipStream_t stream)
     const bool u0 = u1 || p.epi == PC_EPI_RES_GELU || p.epi == PC_EPI_RES || p.epi == PC_EPI_GDN || p.epi == PC_EPI_IGDN || p.epi == PC_EPI_LRP ||
                     p.epi == PC_EPI_LEAKY_RES || p.epi == PC_EPI_SE_ADD;                       // epilogue_uses_aux0
     const size_t stage_bytes = (size_t)S * (BM + BN) * (BK / 4) * 16, epi_bytes = !p.dense_out ? 0 : (u1 ? 32768 : (u0 ? 16384 : 0));
+    if (plan) {
+        // what the kernel will do, for the tests (tests/test_gpu_conv_matrix.py): the instantiation, and the epilogue form chosen at the
+        // end of conv_igemm_uni_kernel from the same launch parameters (nchw_ps / fast / direct there)
+        plan[0] = (DBG != 0) ? PC_PLAN_UNI_OTHER
+                : (SQ && BK == 32 && S == 2 && TM == 1 && TN == 1) ? PC_PLAN_UNI_32_2_SQ
+                : (SQ || TM != 1 || TN != 1) ? PC_PLAN_UNI_OTHER
+                : (BK == 16 && S == 3) ? PC_PLAN_UNI_16_3 : (BK == 32 && S == 2) ? PC_PLAN_UNI_32_2 : (BK == 32 && S == 3) ? PC_PLAN_UNI_32_3
+                : PC_PLAN_UNI_OTHER;
+        const bool nchw_ps = TM * TN == 1 && p.pixel_shuffle && !p.dense_out && !u0 && p.out_sx == 1 && p.osx == 1 && p.osy == 1 && p.Wo % 32 == 0 &&
+                             p.M % 32 == 0 && (p.Cout & 3) == 0 && stage_bytes >= (size_t)4 * 1056 * 4;
+        const bool fast = TM * TN == 1 && p.out_sc == 1 && (p.dense_out || !u0) && p.epi != PC_EPI_SE_ADD;
+        const bool direct = p.dense_out && !p.rowperm && (int64_t)32 * p.out_sx * 4 < ((int64_t)1 << 31);
+        plan[1] = nchw_ps ? PC_FORM_NCHW_PS : (!fast ? PC_FORM_SLOW : (direct ? PC_FORM_DIRECT : PC_FORM_TABLE));
+    }
     // stages (or the epilogue's aux tiles, whichever is larger), then the run table of the K loop / the epilogue's row tables (256 B per wave)
     const size_t lds = std::max(stage_bytes, epi_bytes) + std::max((size_t)tmax * p.nseg * 2 * sizeof(pc_run), (size_t)1024);
     const int MT = (p.M + BM - 1) / BM, NT = (p.Cout + BN - 1) / BN, NZ = p.ngroup == 2 ? 2 : p.nphase;
@@ -1637,8 +1651,15 @@ hipError_t launch_uni(const pc_conv_params& p, hipStream_t stream)
 }
 
 template <int BM, int BN, int WAVES_M, int WAVES_N, bool SMALLC>
-hipError_t launch_cfg(const pc_conv_params& p, hipStream_t stream)
+hipError_t launch_cfg(const pc_conv_params& p, hipStream_t stream, int* plan)
 {
+    if (plan) {
+        plan[0] = BM == 64 ? (SMALLC ? PC_PLAN_L0_64x64_SMALLC : PC_PLAN_L0_64x64)
+                : BN == 32 ? (SMALLC ? PC_PLAN_L0_128x32_SMALLC : PC_PLAN_L0_128x32) : (SMALLC ? PC_PLAN_L0_128x128_SMALLC : PC_PLAN_L0_128x128);
+        const bool u0 = p.epi == PC_EPI_RES_GELU || p.epi == PC_EPI_RES || p.epi == PC_EPI_GATE || p.epi == PC_EPI_GDN || p.epi == PC_EPI_IGDN ||
+                        p.epi == PC_EPI_LRP || p.epi == PC_EPI_LRP_ADD || p.epi == PC_EPI_LEAKY_RES || p.epi == PC_EPI_SE_ADD;   // epilogue_uses_aux0
+        plan[1] = (p.dense_out && p.out_sc == 1 && !u0 && (int64_t)32 * p.out_sx * 4 < ((int64_t)1 << 31)) ? PC_FORM_L0_DIRECT : PC_FORM_L0_GENERIC;
+    }
     dim3 grid((p.M + BM - 1) / BM, (p.Cout + BN - 1) / BN, p.nphase);
     hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WAVES_M, WAVES_N, SMALLC>), grid, dim3(256), 0, stream, p);
     return hipGetLastError();
@@ -1659,7 +1680,7 @@ int pc_conv_weight_layout(int kind, int Cin, int Cout, int k)
 }
 
 // Host-side validation + tile selection.  Returns a pc status code.
-int pc_conv_launch(const pc_conv_params& p_in, hipStream_t stream)
+int pc_conv_launch(const pc_conv_params& p_in, hipStream_t stream, int* plan)
 {
     pc_conv_params p = p_in;                               // derived fields (row table, fast-path flags, debug bits) are set on a private copy
     p.rowtab = nullptr;
@@ -1738,6 +1759,7 @@ int pc_conv_launch(const pc_conv_params& p_in, hipStream_t stream)
                 return PC_ERR_HIP;
             attr_set.fetch_or(1u << (dev & 31), std::memory_order_release);
         }
+        if (plan) { plan[0] = PC_PLAN_IN_GDN; plan[1] = PC_FORM_IN_GDN; }
         hipLaunchKernelGGL(conv_igemm_in_gdn_kernel, dim3((unsigned)((p.M + 63) / 64)), dim3(256), lds, stream, p);
         return hipGetLastError() == hipSuccess ? PC_OK : PC_ERR_HIP;
     }
@@ -1777,27 +1799,27 @@ int pc_conv_launch(const pc_conv_params& p_in, hipStream_t stream)
             int tm = tm_env ? tm_env : (nb64 >= tm_thr ? 2 : 1), tn = tn_env ? tn_env : 1;
             const int Su = s_env ? s_env : ((chunks <= 8 || tm * tn > 1) ? 2 : 3);
             const int ab = (p.dbg & 64) ? 0 : (p.dbg & 15);                   // ablation builds of the 64x64 three-stage instantiation
-            if (p.square) e = launch_uni<32, 2, 1, 1, true>(p, stream);
+            if (p.square) e = launch_uni<32, 2, 1, 1, true>(p, stream, plan);
 #ifdef PC_CONV_TUNING   // ablation builds of the 64x64 three-stage instantiation (make FLAGS+=-DPC_CONV_TUNING): no MFMAs / no DMA issue / zero-fill DMAs / no operand reads ...
-            else if (ab == 1) e = launch_uni<32, 3, 1, 1, false, 1>(p, stream);
-            else if (ab == 2) e = launch_uni<32, 3, 1, 1, false, 2>(p, stream);
-            else if (ab == 4) e = launch_uni<32, 3, 1, 1, false, 4>(p, stream);
-            else if (ab == 8) e = launch_uni<32, 3, 1, 1, false, 8>(p, stream);
-            else if (ab == 10) e = launch_uni<32, 3, 1, 1, false, 10>(p, stream);
-            else if (ab == 3) e = launch_uni<32, 3, 1, 1, false, 3>(p, stream);
-            else if (ab == 0 && (p.dbg & 16) && !(p.dbg & 64)) e = launch_uni<32, 3, 1, 1, false, 16>(p, stream);
-            else if ((p.dbg & 64) && (p.dbg & 8)) e = launch_uni<32, 3, 1, 1, false, 74>(p, stream);
+            else if (ab == 1) e = launch_uni<32, 3, 1, 1, false, 1>(p, stream, plan);
+            else if (ab == 2) e = launch_uni<32, 3, 1, 1, false, 2>(p, stream, plan);
+            else if (ab == 4) e = launch_uni<32, 3, 1, 1, false, 4>(p, stream, plan);
+            else if (ab == 8) e = launch_uni<32, 3, 1, 1, false, 8>(p, stream, plan);
+            else if (ab == 10) e = launch_uni<32, 3, 1, 1, false, 10>(p, stream, plan);
+            else if (ab == 3) e = launch_uni<32, 3, 1, 1, false, 3>(p, stream, plan);
+            else if (ab == 0 && (p.dbg & 16) && !(p.dbg & 64)) e = launch_uni<32, 3, 1, 1, false, 16>(p, stream, plan);
+            else if ((p.dbg & 64) && (p.dbg & 8)) e = launch_uni<32, 3, 1, 1, false, 74>(p, stream, plan);
 #endif
-            else if ((p.dbg & 64) && bk == 16) e = launch_uni<16, 3, 1, 1, false, 64>(p, stream);   // timeline of the default large-grid instantiation (PC_CONV_BK=16)
-            else if (p.dbg & 64) e = launch_uni<32, 3, 1, 1, false, 64>(p, stream);
-            else if (bk == 16 && tm == 1 && tn == 1 && s_env == 2) e = launch_uni<16, 2, 1, 1>(p, stream);
-            else if (bk == 16 && tm == 1 && tn == 1 && s_env == 3) e = launch_uni<16, 3, 1, 1>(p, stream);
-            else if (bk == 16 && tm == 1 && tn == 1) e = launch_uni<16, 4, 1, 1>(p, stream);
-            else if (policy == 1 && !s_env && !tm_env && !tn_env) e = launch_uni<16, 3, 1, 1>(p, stream);
-            else if (policy == 2 && !s_env && !tm_env && !tn_env && tm == 1) e = launch_uni<16, 3, 1, 1>(p, stream);
-            else if (policy == 3 && !s_env && !tm_env && !tn_env && nb64 > small_thr) e = launch_uni<16, 3, 1, 1>(p, stream);
-            else if (policy == 3 && !s_env && !tm_env && !tn_env) e = chunks <= 8 ? launch_uni<32, 2, 1, 1>(p, stream) : launch_uni<32, 3, 1, 1>(p, stream);
-#define PC_UNI_CASE(S_, TM_, TN_) else if (Su == S_ && tm == TM_ && tn == TN_) e = launch_uni<32, S_, TM_, TN_>(p, stream);
+            else if ((p.dbg & 64) && bk == 16) e = launch_uni<16, 3, 1, 1, false, 64>(p, stream, plan);   // timeline of the default large-grid instantiation (PC_CONV_BK=16)
+            else if (p.dbg & 64) e = launch_uni<32, 3, 1, 1, false, 64>(p, stream, plan);
+            else if (bk == 16 && tm == 1 && tn == 1 && s_env == 2) e = launch_uni<16, 2, 1, 1>(p, stream, plan);
+            else if (bk == 16 && tm == 1 && tn == 1 && s_env == 3) e = launch_uni<16, 3, 1, 1>(p, stream, plan);
+            else if (bk == 16 && tm == 1 && tn == 1) e = launch_uni<16, 4, 1, 1>(p, stream, plan);
+            else if (policy == 1 && !s_env && !tm_env && !tn_env) e = launch_uni<16, 3, 1, 1>(p, stream, plan);
+            else if (policy == 2 && !s_env && !tm_env && !tn_env && tm == 1) e = launch_uni<16, 3, 1, 1>(p, stream, plan);
+            else if (policy == 3 && !s_env && !tm_env && !tn_env && nb64 > small_thr) e = launch_uni<16, 3, 1, 1>(p, stream, plan);
+            else if (policy == 3 && !s_env && !tm_env && !tn_env) e = chunks <= 8 ? launch_uni<32, 2, 1, 1>(p, stream, plan) : launch_uni<32, 3, 1, 1>(p, stream, plan);
+#define PC_UNI_CASE(S_, TM_, TN_) else if (Su == S_ && tm == TM_ && tn == TN_) e = launch_uni<32, S_, TM_, TN_>(p, stream, plan);
             PC_UNI_CASE(3, 1, 1) PC_UNI_CASE(2, 1, 1) PC_UNI_CASE(3, 2, 1) PC_UNI_CASE(2, 2, 1) PC_UNI_CASE(2, 1, 2)
             PC_UNI_CASE(2, 2, 2)
 #undef PC_UNI_CASE
@@ -1808,9 +1830,9 @@ int pc_conv_launch(const pc_conv_params& p_in, hipStream_t stream)
         int cfg = p.tile_cfg;
         if (cfg == PC_TILE_AUTO) cfg = (p.Cout <= 4) ? PC_TILE_128x32 : PC_TILE_64x64;
         switch (cfg) {
-        case PC_TILE_128x128: e = p.smallc ? launch_cfg<128, 128, 2, 2, true>(p, stream) : launch_cfg<128, 128, 2, 2, false>(p, stream); break;
-        case PC_TILE_64x64: e = p.smallc ? launch_cfg<64, 64, 2, 2, true>(p, stream) : launch_cfg<64, 64, 2, 2, false>(p, stream); break;
-        case PC_TILE_128x32: e = p.smallc ? launch_cfg<128, 32, 4, 1, true>(p, stream) : launch_cfg<128, 32, 4, 1, false>(p, stream); break;
+        case PC_TILE_128x128: e = p.smallc ? launch_cfg<128, 128, 2, 2, true>(p, stream, plan) : launch_cfg<128, 128, 2, 2, false>(p, stream, plan); break;
+        case PC_TILE_64x64: e = p.smallc ? launch_cfg<64, 64, 2, 2, true>(p, stream, plan) : launch_cfg<64, 64, 2, 2, false>(p, stream, plan); break;
+        case PC_TILE_128x32: e = p.smallc ? launch_cfg<128, 32, 4, 1, true>(p, stream, plan) : launch_cfg<128, 32, 4, 1, false>(p, stream, plan); break;
         default: return PC_ERR_ARG;
         }
     }

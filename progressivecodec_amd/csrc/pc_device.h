@@ -99,7 +99,8 @@ struct pc_conv_params {
     int dbg;                                 // tuning only (PC_CONV_DBG bits): 1 skip MFMAs, 2 skip DMA issue, 4 DMAs read the zero page, 64 stamps, 256 print occupancy
 };
 
-int pc_conv_launch(const pc_conv_params& p, hipStream_t stream);
+// plan (optional, host side): [0] the instantiation chosen (PC_PLAN_*), [1] the epilogue form it takes (PC_FORM_*; include/pcodec.h)
+int pc_conv_launch(const pc_conv_params& p, hipStream_t stream, int* plan = nullptr);
 // row-table cache (pc_conv.hip): owned by a codec, freed with it; cap_bytes bounds the HBM it may hold (LRU eviction)
 struct pc_rowtab_cache;
 pc_rowtab_cache* pc_rowtab_cache_create(size_t cap_bytes);
