@@ -229,6 +229,31 @@ PC_API int pc_codec_set_rem_checkpoint(pc_codec* c, const float* checkpoint_rep)
  * clamp01(refine(clamp01(g_s(y_hat)))) on the padded image -- except under REM (pc_codec_set_rem n > 0), whose reference calls g_s
  * directly (models/CHProgREM.py:977,1123).  Encoder output does not change. */
 PC_API int pc_codec_set_post_filter(pc_codec* c, int mode);
+/* The topology switches of ChannelProgresssiveWACNN (models/CHProg_cnn.py:29-49) beyond the canonical configuration.  Every field's
+ * zero is the canonical value, so a zero-initialised struct (the object's default) is multiple_hyperprior = delta_encode = True,
+ * joiner_policy "res", support_progressive_slices 5 and the other switches False.
+ *   support_deficit      5 - support_progressive_slices (0..5): determine_support keeps the last min(S, i) enhancement entries (:377-383)
+ *                        and the prog stacks are 320 + 32 min(i+1, S+1) / LRP 320 + 32 min(i+2, S+2) channels wide (:235-274)
+ *   no_delta_encode      delta_encode = False: the enhancement slice is coded without subtracting the raw base slice (:780-781)
+ *   single_hyperprior    multiple_hyperprior = False: one h_mean_s / h_scale_s pair with 640 outputs, keys h_mean_s.<layer> (:705-715)
+ *   joiner_cond          joiner_policy "cond": merge = joiner[i](cat(enhanced slice, base slice i)), keys joiner.<i>.{0,2,4} (:117-126,385-393)
+ *   all_scalable         mean / scale support from mu_total / std_total instead of the merged slices (:784-785)
+ *   total_mu_rep         mu_total holds mu + y_hat_base[i] (:801-810)
+ *   support_std          std_total holds the raw scale instead of mu_total's entry (:802-805)
+ *   residual_before_lrp  forward only: merge before the LRP (:1153-1164)
+ * Call before pc_codec_finalize (PC_ERR_STATE after it, or on a WACNN object); PC_ERR_ARG for a field out of range.  The tensors
+ * finalize expects follow the topology.  Results of the canonical topology never change. */
+typedef struct pc_topology {
+    int support_deficit;
+    int no_delta_encode;
+    int single_hyperprior;
+    int joiner_cond;
+    int all_scalable;
+    int total_mu_rep;
+    int support_std;
+    int residual_before_lrp;
+} pc_topology;
+PC_API int pc_codec_set_topology(pc_codec* c, const pc_topology* t);
 /* refine(x) (mode 1, which 0) or refine[which](x) (mode 2), unclamped: x and out device NCHW float [B][3][H][W], out may be x.  H and W
  * must be multiples of 4 (PC_ERR_ARG otherwise, where the reference fails in torch.cat); PC_ERR_STATE without a filter.  Scratch: 864
  * bytes per pixel of the batch, kept by the object (section 6 of DESIGN.md). */

@@ -24,7 +24,7 @@ EXPORTS = [
     "pc_codec_host_stats", "pc_codec_set_rem_checkpoint", "pc_codec_set_option", "pc_selftest_packed_gelu", "pc_profile_set_epoch", "pc_codec_profile_intervals",
     "pc_codec_set_post_filter", "pc_codec_post_filter",
     "pc_codec_set_model", "pc_codec_wacnn_compress", "pc_codec_wacnn_decompress", "pc_codec_wacnn_forward",
-    "pc_test_conv",
+    "pc_test_conv", "pc_codec_set_topology",
 ]
 
 
@@ -97,6 +97,7 @@ def lib():
         L.pc_codec_set_post_filter.argtypes = [vp, C.c_int]
         L.pc_codec_post_filter.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp]
         L.pc_codec_set_model.argtypes = [vp, C.c_int]
+        L.pc_codec_set_topology.argtypes = [vp, vp]
         L.pc_codec_wacnn_compress.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp]
         L.pc_codec_wacnn_decompress.argtypes = [vp, vp, sz, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]
         L.pc_codec_wacnn_forward.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]

@@ -37,6 +37,12 @@ class CodecConfig:
     scales_max: float = 256.0
     scales_levels: int = 64
     u_net_post: int = 0          # CHProg_cnn.py:87-88,277-284: 0 none, 1 refine, 2 two refine nets (decoding uses refine[1])
+    # the remaining topology switches (CHProg_cnn.py:29-49, utils/parser.py:29-34); False is the canonical value of each
+    all_scalable: bool = False         # enhancement support from mu_total / std_total (:784-785)
+    total_mu_rep: bool = False         # mu_total holds mu + y_hat_base[i] (:800)
+    support_std: bool = False          # std_total holds the raw scale (:802-805)
+    residual_before_lrp: bool = False  # forward_single_quality only: merge before the LRP (:1153-1164)
+    double_dim: bool = False           # read by the learnable mask policies only (layers/masking.py), accepted and ignored
 
     @property
     def ns0(self):
@@ -46,20 +52,38 @@ class CodecConfig:
     def ns1(self):
         return self.division_dimension[1] // self.dim_chunk
 
+    @property
+    def canonical_topology(self):
+        """True for the topology the authors ran (module docstring); False when any switch of pc_topology is set."""
+        return (self.multiple_hyperprior and self.delta_encode and self.joiner_policy == "res" and self.support_progressive_slices == 5
+                and not (self.all_scalable or self.total_mu_rep or self.support_std or self.residual_before_lrp))
+
+    def topology(self):
+        """the pc_topology fields (include/pcodec.h), in their order: every zero is the canonical value"""
+        return (5 - self.support_progressive_slices, int(not self.delta_encode), int(not self.multiple_hyperprior),
+                int(self.joiner_policy == "cond"), int(self.all_scalable), int(self.total_mu_rep), int(self.support_std),
+                int(self.residual_before_lrp))
+
     def check_supported(self):
-        """The native runtime implements the canonical topology, with one encoder (WACNN's 3 -> M g_a, cnn.py:34-44) or with
-        multiple_encoder=True (two 3 -> 320 encoders whose outputs are concatenated, CHProg_cnn.py:131-144,691-697)."""
-        ok = (self.multiple_decoder and self.multiple_hyperprior
-              and self.delta_encode and self.joiner_policy == "res"
-              and self.support_progressive_slices == 5 and self.max_support_slices == 5
-              and self.dim_chunk == 32 and tuple(self.division_dimension) == (320, 640)
-              and self.N == 192 and self.M == 640)
+        """The native runtime implements N=192, M=640, division_dimension (320, 640), dim_chunk 32, multiple_decoder=True, with one
+        encoder (WACNN's 3 -> M g_a, cnn.py:34-44) or multiple_encoder=True (two 3 -> 320 encoders whose outputs are concatenated,
+        CHProg_cnn.py:131-144,691-697), and every value of the topology switches multiple_hyperprior, delta_encode,
+        support_progressive_slices (0..5), joiner_policy "res" / "cond", all_scalable, total_mu_rep, support_std, residual_before_lrp
+        and double_dim.  Refused: multiple_decoder=False (the reference's g_s is built for 640 input channels and receives 320) and
+        joiner_policy "channel_cond" / "channel_res" (the reference builds no joiner for them)."""
         if self.u_net_post not in (0, 1, 2):
             raise AssertionError("u_net_post must be 0, 1 or 2 (CHProg_cnn.py:88); got %r" % (self.u_net_post,))
+        if self.joiner_policy not in ("res", "cond", "channel_cond", "channel_res"):
+            raise AssertionError("joiner_policy must be res, cond, channel_cond or channel_res (CHProg_cnn.py:55); got %r" % (self.joiner_policy,))
+        ok = (self.multiple_decoder and self.joiner_policy in ("res", "cond")
+              and isinstance(self.support_progressive_slices, int) and 0 <= self.support_progressive_slices <= 5
+              and self.max_support_slices == 5
+              and self.dim_chunk == 32 and tuple(self.division_dimension) == (320, 640)
+              and self.N == 192 and self.M == 640)
         if not ok:
             raise NotImplementedError(
-                "progressivecodec_amd implements the canonical ProgressiveCodec configuration only "
-                "(SURVEY.md section 8); got %r" % (self,))
+                "progressivecodec_amd implements ProgressiveCodec with N=192, M=640, division_dimension (320, 640), dim_chunk 32, "
+                "multiple_decoder=True, joiner_policy res / cond and support_progressive_slices 0..5 (SURVEY.md section 8); got %r" % (self,))
 
 
 CC_WIDTHS = (224, 176, 128, 64, 32)  # CHProg_cnn.py:167-175
@@ -164,10 +188,16 @@ def param_spec(cfg: CodecConfig = CodecConfig()) -> "OrderedDict[str, tuple]":
     # module registration order in the reference: WACNN.__init__ registers h_a, h_mean_s, h_scale_s,
     # cc_mean, cc_scale, lrp, entropy_bottleneck, gaussian_conditional; the subclass re-assigns
     # g_s, cc_*, lrp, h_*_s in place and appends the *_prog families.
-    for k in range(2):
-        _hs(f"h_mean_s.{k}")
-    for k in range(2):
-        _hs(f"h_scale_s.{k}")
+    if cfg.multiple_hyperprior:
+        for k in range(2):
+            _hs(f"h_mean_s.{k}")
+        for k in range(2):
+            _hs(f"h_scale_s.{k}")
+    else:  # WACNN's own pair (cnn.py:69-91), M outputs, keys without a ModuleList index
+        for p in ("h_mean_s", "h_scale_s"):
+            _hs(p)
+            s[p + ".8.weight"] = ((M, 288, 3, 3), "float32", "conv_w")
+            s[p + ".8.bias"] = ((M,), "float32", "conv_b")
     for fam in ("cc_mean_transforms", "cc_scale_transforms", "lrp_transforms"):
         for i in range(cfg.ns0):
             _stack5(s, f"{fam}.{i}", cc_in_channels(cfg, fam, i))
@@ -192,6 +222,11 @@ def param_spec(cfg: CodecConfig = CodecConfig()) -> "OrderedDict[str, tuple]":
     s[f"{gc}.scale_bound"] = ((1,), "float32", "scale_bound")
     s[f"{gc}.likelihood_lower_bound.bound"] = ((1,), "float32", "likelihood_bound")
     s[f"{gc}.lower_bound_scale.bound"] = ((1,), "float32", "scale_bound")
+    if cfg.joiner_policy == "cond":  # CHProg_cnn.py:117-126, registered by the subclass before the *_prog families
+        for i in range(cfg.ns0):
+            _conv(s, f"joiner.{i}.0", 2 * cfg.dim_chunk, 64, 3)
+            _conv(s, f"joiner.{i}.2", 64, 64, 3)
+            _conv(s, f"joiner.{i}.4", 64, cfg.dim_chunk, 3)
     for fam in ("cc_mean_transforms_prog", "cc_scale_transforms_prog", "lrp_transforms_prog"):
         for i in range(cfg.ns0):
             _stack5(s, f"{fam}.{i}", cc_in_channels(cfg, fam, i))

@@ -100,7 +100,9 @@ struct pc_codec {
     int post_mode = 0;                           // u_net_post (pc_codec_set_post_filter): 0 none, 1 refine, 2 refine[0..1] (decode uses refine[1])
     UnetW unet[2];                               // [0] refine (mode 1) / refine[0] (mode 2), [1] refine[1] (mode 2)
     ConvW ha[5];
-    HsW hms[2], hss[2];
+    HsW hms[2], hss[2];                          // single_hyperprior: [1] is the one 640-output pair, [0] the same nets with its first 320 outputs
+    pc_topology topo{};                          // pc_codec_set_topology: zero = the canonical topology
+    ConvW joiner[NS0][3];                        // joiner_policy "cond": joiner[i].{0,2,4} (CHProg_cnn.py:117-126)
     Stack5W cc_mean[NS0], cc_scale[NS0], lrp[NS0], cc_mean_p[NS0], cc_scale_p[NS0], lrp_p[NS0];
     float* medians = nullptr;                    // [192] device
     const float* cust_map = nullptr;             // pc_codec_set_cust_map: consumed by the next compress / decompress call
@@ -450,14 +452,15 @@ void fill_deconv_taps(pc_conv_params& q)   // ConvTranspose2d(5, s2, p2, op1) as
 // generic conv over NHWC segments -> NHWC output slice (channel offset folded into `out`, pixel stride ldo)
 struct Group1 { const ConvW* w; const float* seg0; float* out; };   // second GEMM of a grouped launch
 
-int conv(hipStream_t st, const ConvW& w, std::initializer_list<Seg> segs, int B, int H, int W, int stride,
-         float* out, int ldo, int epi, const float* aux0 = nullptr, int ld0 = 0, const float* aux1 = nullptr, int ld1 = 0,
-         bool pixel_shuffle = false, const Group1* g1 = nullptr, float* out_relu = nullptr)
+int conv_n(hipStream_t st, const ConvW& w, const Seg* segs, int nseg, int B, int H, int W, int stride,
+           float* out, int ldo, int epi, const float* aux0 = nullptr, int ld0 = 0, const float* aux1 = nullptr, int ld1 = 0,
+           bool pixel_shuffle = false, const Group1* g1 = nullptr, float* out_relu = nullptr)
 {
     pc_conv_params q;
     std::memset(&q, 0, sizeof(q));
     int cin = 0;
-    for (const Seg& s : segs) {
+    for (int j = 0; j < nseg; ++j) {
+        const Seg& s = segs[j];
         if (s.nch == 0) continue;
         if (q.nseg >= PC_MAX_SEG) return PC_ERR_ARG;
         q.seg[q.nseg].ptr = s.p; q.seg[q.nseg].ld = s.ld; q.seg[q.nseg].nch = s.nch; ++q.nseg; cin += s.nch;
@@ -485,6 +488,13 @@ int conv(hipStream_t st, const ConvW& w, std::initializer_list<Seg> segs, int B,
         q.ngroup = 2; q.g1_seg0 = g1->seg0; q.g1_w = g1->w->w; q.g1_bias = g1->w->b; q.g1_out = g1->out;
     }
     return launch_conv(q, st);
+}
+
+int conv(hipStream_t st, const ConvW& w, std::initializer_list<Seg> segs, int B, int H, int W, int stride,
+         float* out, int ldo, int epi, const float* aux0 = nullptr, int ld0 = 0, const float* aux1 = nullptr, int ld1 = 0,
+         bool pixel_shuffle = false, const Group1* g1 = nullptr, float* out_relu = nullptr)
+{
+    return conv_n(st, w, segs.begin(), (int)segs.size(), B, H, W, stride, out, ldo, epi, aux0, ld0, aux1, ld1, pixel_shuffle, g1, out_relu);
 }
 
 int gdn(hipStream_t st, const GdnW& g, const float* x, int B, int H, int W, bool inverse, float* out)
@@ -540,15 +550,14 @@ int wam(pc_codec* c, hipStream_t st, const WamW& w, const float* x, int B, int H
     return PC_OK;
 }
 
-int stack5(pc_codec* c, hipStream_t st, const Stack5W& s, std::initializer_list<Seg> segs, int B, int h, int w,
-           float* out, int ldo, int epi, const float* aux0 = nullptr, int ld0 = 0, const float* aux1 = nullptr, int ld1 = 0,
-           const char* tag = "s5")
+int stack5_n(pc_codec* c, hipStream_t st, const Stack5W& s, const Seg* segs, int nseg, int B, int h, int w, float* out, int ldo, int epi,
+             const char* tag, const float* aux0 = nullptr, int ld0 = 0, const float* aux1 = nullptr, int ld1 = 0)
 {
     const size_t M = (size_t)B * h * w;
     float *t0, *t1;
     PCCHK(c->buf(std::string(tag) + "_t0", M * 224, &t0));
     PCCHK(c->buf(std::string(tag) + "_t1", M * 176, &t1));
-    PCCHK(conv(st, s.c[0], segs, B, h, w, 1, t0, 224, PC_EPI_GELU));
+    PCCHK(conv_n(st, s.c[0], segs, nseg, B, h, w, 1, t0, 224, PC_EPI_GELU));
     PCCHK(conv(st, s.c[1], {{t0, 224, 224}}, B, h, w, 1, t1, 176, PC_EPI_GELU));
     PCCHK(conv(st, s.c[2], {{t1, 176, 176}}, B, h, w, 1, t0, 128, PC_EPI_GELU));
     PCCHK(conv(st, s.c[3], {{t0, 128, 128}}, B, h, w, 1, t1, 64, PC_EPI_GELU));
@@ -556,10 +565,17 @@ int stack5(pc_codec* c, hipStream_t st, const Stack5W& s, std::initializer_list<
     return PC_OK;
 }
 
+int stack5(pc_codec* c, hipStream_t st, const Stack5W& s, std::initializer_list<Seg> segs, int B, int h, int w,
+           float* out, int ldo, int epi, const float* aux0 = nullptr, int ld0 = 0, const float* aux1 = nullptr, int ld1 = 0,
+           const char* tag = "s5")
+{
+    return stack5_n(c, st, s, segs.begin(), (int)segs.size(), B, h, w, out, ldo, epi, tag, aux0, ld0, aux1, ld1);
+}
+
 // cc_mean || cc_scale of one chain step as five grouped launches (identical shapes; the supports differ only in
 // their first segment: latent_means vs latent_scales)
-int stack5_pair(pc_codec* c, hipStream_t st, const Stack5W& sm, const Stack5W& ss, std::initializer_list<Seg> segs_mean,
-                const float* seg0_scale, int B, int h, int w, float* out_mean, float* out_scale, const char* tagm, const char* tags)
+int stack5_pair_n(pc_codec* c, hipStream_t st, const Stack5W& sm, const Stack5W& ss, const Seg* segs_mean, int nseg,
+                  const float* seg0_scale, int B, int h, int w, float* out_mean, float* out_scale, const char* tagm, const char* tags)
 {
     const size_t M = (size_t)B * h * w;
     float *m0, *m1, *s0, *s1;
@@ -568,7 +584,7 @@ int stack5_pair(pc_codec* c, hipStream_t st, const Stack5W& sm, const Stack5W& s
     PCCHK(c->buf(std::string(tags) + "_t0", M * 224, &s0));
     PCCHK(c->buf(std::string(tags) + "_t1", M * 176, &s1));
     Group1 g{&ss.c[0], seg0_scale, s0};
-    PCCHK(conv(st, sm.c[0], segs_mean, B, h, w, 1, m0, 224, PC_EPI_GELU, nullptr, 0, nullptr, 0, false, &g));
+    PCCHK(conv_n(st, sm.c[0], segs_mean, nseg, B, h, w, 1, m0, 224, PC_EPI_GELU, nullptr, 0, nullptr, 0, false, &g));
     g = Group1{&ss.c[1], s0, s1};
     PCCHK(conv(st, sm.c[1], {{m0, 224, 224}}, B, h, w, 1, m1, 176, PC_EPI_GELU, nullptr, 0, nullptr, 0, false, &g));
     g = Group1{&ss.c[2], s1, s0};
@@ -578,6 +594,12 @@ int stack5_pair(pc_codec* c, hipStream_t st, const Stack5W& sm, const Stack5W& s
     g = Group1{&ss.c[4], s1, out_scale};
     PCCHK(conv(st, sm.c[4], {{m1, 64, 64}}, B, h, w, 1, out_mean, SLICE, PC_EPI_NONE, nullptr, 0, nullptr, 0, false, &g));
     return PC_OK;
+}
+
+int stack5_pair(pc_codec* c, hipStream_t st, const Stack5W& sm, const Stack5W& ss, std::initializer_list<Seg> segs_mean,
+                const float* seg0_scale, int B, int h, int w, float* out_mean, float* out_scale, const char* tagm, const char* tags)
+{
+    return stack5_pair_n(c, st, sm, ss, segs_mean.begin(), (int)segs_mean.size(), seg0_scale, B, h, w, out_mean, out_scale, tagm, tags);
 }
 
 // hyper-synthesis net (CHProg_cnn.py:208-232): z_hat [B][zh][zw][192] -> out slice [B][4zh][4zw][320] (ld 640)
@@ -834,6 +856,11 @@ int hyper(pc_codec* c, hipStream_t st, const float* z_hat, int B, int zh, int zw
     // (base only) or four nets side by side on streams of their own was worth 1 % in round 1; with the encoder / decoder objects side
     // by side and the chains pipelined it cost 3 % of the overlapped bench and 2-5 % of the sequential one
     // (profiles/r03_t_hyper_parallel_ab.log): four more streams' launches in a chip that is already shared by four chains.  Removed.
+    if (quality != 0 && c->topo.single_hyperprior) {   // one 640-output pair: the enhancement chain reads its channels [320:]
+        PCCHK(hs(c, st, c->hss[1], z_hat, B, zh, zw, ls, MLAT));
+        PCCHK(hs(c, st, c->hms[1], z_hat, B, zh, zw, lm, MLAT));
+        return PC_OK;
+    }
     PCCHK(hs(c, st, c->hss[0], z_hat, B, zh, zw, ls, MLAT));
     PCCHK(hs(c, st, c->hms[0], z_hat, B, zh, zw, lm, MLAT));
     if (quality != 0) {                           // CHProg_cnn.py:708-715
@@ -969,7 +996,7 @@ namespace {
 int prep_encode(const float* scale, int ld_scale, const float* mu, int ld_mu, const float* y, int ld_y, const float* ybase, int ld_ybase,
                 const float* thr, int mask_mode, int B, int HW, const float* scale_table, int n_table, float scale_bound, int32_t* sym,
                 int32_t* idx, float* mask, float* yhat, int ld_yhat, float* lik, int64_t lik_sb, hipStream_t stream,
-                const float* mask_src = nullptr, int64_t mask_sb = 0)
+                const float* mask_src = nullptr, int64_t mask_sb = 0, const float* yadd = nullptr, int ld_yadd = 0)
 {
     if (!scale || !mu || !y || !sym || !idx || !yhat || !scale_table || (mask_mode == 1 && !thr)) return PC_ERR_ARG;
     pc_prep_params p;
@@ -980,6 +1007,7 @@ int prep_encode(const float* scale, int ld_scale, const float* mu, int ld_mu, co
     p.table = scale_table; p.ntable = n_table; p.bound = scale_bound;
     p.sym = sym; p.idx = idx; p.mask = mask; p.yhat = yhat; p.ld_yhat = ld_yhat;
     p.lik = lik; p.lik_sb = lik_sb; p.mask_src = mask_src; p.mask_sb = mask_sb;
+    p.yadd = yadd; p.ld_yadd = ld_yadd;
     return pc_prep_enc_launch(p, stream);
 }
 }  // namespace
@@ -1147,18 +1175,48 @@ int load_channel(pc_codec* c)
     }
     const int ha_c[6] = {MLAT, 320, 288, 256, 224, NCH};
     for (int j = 0; j < 5; ++j) PCCHK(load_conv(c, "h_a." + std::to_string(2 * j), ha_c[j], ha_c[j + 1], 3, 0, &c->ha[j]));
-    for (int k = 0; k < 2; ++k) {
-        PCCHK(load_hs(c, "h_mean_s." + std::to_string(k), &c->hms[k]));
-        PCCHK(load_hs(c, "h_scale_s." + std::to_string(k), &c->hss[k]));
+    if (c->topo.single_hyperprior) {
+        // one WACNN-form pair with 640 outputs, keys without a ModuleList index (cnn.py:69-91, CHProg_cnn.py:705-715): [1] is the whole
+        // net; [0] shares its first four layers and keeps the first 320 outputs of the last (each output channel is its own chain, so
+        // its values are those of the 640-output conv -- the base-only hyper-synthesis of a quality-0 call computes just these)
+        for (int which = 0; which < 2; ++which) {
+            const std::string p = which == 0 ? "h_mean_s" : "h_scale_s";
+            HsW* h = which == 0 ? c->hms : c->hss;
+            PCCHK(load_conv(c, p + ".0", NCH, 192, 3, 0, &h[1].c0));
+            PCCHK(load_conv(c, p + ".2.0", 192, 224 * 4, 3, 0, &h[1].c2));
+            PCCHK(load_conv(c, p + ".4", 224, 256, 3, 0, &h[1].c4));
+            PCCHK(load_conv(c, p + ".6.0", 256, 288 * 4, 3, 0, &h[1].c6));
+            PCCHK(load_conv(c, p + ".8", 288, MLAT, 3, 0, &h[1].c8));
+            const HostTensor* w = find(c, p + ".8.weight", PC_F32, {MLAT, 288, 3, 3});
+            const HostTensor* b = find(c, p + ".8.bias", PC_F32, {MLAT});
+            if (!w || !b) return PC_ERR_MISSING;
+            HostTensor lw{std::vector<uint8_t>(w->data.begin(), w->data.begin() + (size_t)D0 * 288 * 9 * 4), {D0, 288, 3, 3}, PC_F32};
+            HostTensor lb{std::vector<uint8_t>(b->data.begin(), b->data.begin() + (size_t)D0 * 4), {D0}, PC_F32};
+            c->sd[p + ".8lo.weight"] = std::move(lw);
+            c->sd[p + ".8lo.bias"] = std::move(lb);
+            h[0] = h[1];
+            PCCHK(load_conv(c, p + ".8lo", 288, D0, 3, 0, &h[0].c8));
+        }
+    } else {
+        for (int k = 0; k < 2; ++k) {
+            PCCHK(load_hs(c, "h_mean_s." + std::to_string(k), &c->hms[k]));
+            PCCHK(load_hs(c, "h_scale_s." + std::to_string(k), &c->hss[k]));
+        }
     }
+    const int S = 5 - c->topo.support_deficit;                          // support_progressive_slices (CHProg_cnn.py:235-274)
     for (int i = 0; i < NS0; ++i) {
         const std::string s = "." + std::to_string(i);
         PCCHK(load_stack5(c, "cc_mean_transforms" + s, D0 + 32 * std::min(i, 5), &c->cc_mean[i]));
         PCCHK(load_stack5(c, "cc_scale_transforms" + s, D0 + 32 * std::min(i, 5), &c->cc_scale[i]));
         PCCHK(load_stack5(c, "lrp_transforms" + s, D0 + 32 * std::min(i + 1, 6), &c->lrp[i]));
-        PCCHK(load_stack5(c, "cc_mean_transforms_prog" + s, D0 + 32 * std::min(i + 1, 6), &c->cc_mean_p[i]));
-        PCCHK(load_stack5(c, "cc_scale_transforms_prog" + s, D0 + 32 * std::min(i + 1, 6), &c->cc_scale_p[i]));
-        PCCHK(load_stack5(c, "lrp_transforms_prog" + s, D0 + 32 * std::min(i + 2, 7), &c->lrp_p[i]));
+        PCCHK(load_stack5(c, "cc_mean_transforms_prog" + s, D0 + 32 * std::min(i + 1, S + 1), &c->cc_mean_p[i]));
+        PCCHK(load_stack5(c, "cc_scale_transforms_prog" + s, D0 + 32 * std::min(i + 1, S + 1), &c->cc_scale_p[i]));
+        PCCHK(load_stack5(c, "lrp_transforms_prog" + s, D0 + 32 * std::min(i + 2, S + 2), &c->lrp_p[i]));
+        if (c->topo.joiner_cond) {
+            PCCHK(load_conv(c, "joiner" + s + ".0", 2 * SLICE, 64, 3, 0, &c->joiner[i][0]));
+            PCCHK(load_conv(c, "joiner" + s + ".2", 64, 64, 3, 0, &c->joiner[i][1]));
+            PCCHK(load_conv(c, "joiner" + s + ".4", 64, SLICE, 3, 0, &c->joiner[i][2]));
+        }
     }
     return PC_OK;
 }
@@ -1295,6 +1353,17 @@ extern "C" int pc_codec_set_model(pc_codec* c, int kind)
     return PC_OK;
 }
 
+extern "C" int pc_codec_set_topology(pc_codec* c, const pc_topology* t)
+{
+    if (!c || !t) return PC_ERR_ARG;
+    if (c->finalized || c->model != PC_MODEL_CHANNEL) return PC_ERR_STATE;
+    if (t->support_deficit < 0 || t->support_deficit > 5) return PC_ERR_ARG;
+    for (int v : {t->no_delta_encode, t->single_hyperprior, t->joiner_cond, t->all_scalable, t->total_mu_rep, t->support_std, t->residual_before_lrp})
+        if (v != 0 && v != 1) return PC_ERR_ARG;
+    c->topo = *t;
+    return PC_OK;
+}
+
 extern "C" int pc_codec_set_post_filter(pc_codec* c, int mode)
 {
     // ChannelProgresssiveWACNN(u_net_post=mode) (CHProg_cnn.py:87-88, 277-284): which refine nets pc_codec_finalize loads
@@ -1392,6 +1461,7 @@ struct ChainCtx {
     int B, h, w, HW;
     size_t M;                                   // B * HW
     float *y, *lm, *ls, *yb, *ye, *mu, *scale, *thr, *masks;
+    float* mut;                                 // total_mu_rep: per enhancement slice mu + y_hat_base[i] (mu_total, CHProg_cnn.py:801-810), or null
     const float *mu_base, *scale_base;          // set 0's per-slice mu / scale: the base half is written there only (second_level_set
                                                 // re-points mu / scale, not these)
     int32_t *sym, *idx;
@@ -1547,6 +1617,55 @@ int rem_refine(const ChainCtx& k, int i, int b0, int nb, float* mu_i, float* sc_
     return pc_rem_combine_launch(x, SLICE, sc_i, SLICE, nb, k.HW, thr2, mode_star, thr2 + k.B, mode_bar, st);
 }
 
+// number of enhancement support entries of slice i: min(support_progressive_slices, i) (determine_support, CHProg_cnn.py:377-383)
+int support_count(const pc_codec* c, int i) { return std::min(5 - c->topo.support_deficit, i); }
+
+// all_scalable: append the support entries [i-s, i) of mu_total (std = false) or std_total (std = true) for images from b0 -- per-step
+// buffers, ld 32, read in place.  mu_total[j] = mu_j, or mu_j + y_hat_base[j] with total_mu_rep; std_total[j] = std_total's entry: the
+// raw (pre-mask) scale_j with support_std, mu_total[j] otherwise (:801-810).  The forward path's std_total has two entries per slice,
+// (that entry, scale_j) (:1123-1128), and slice i reads entries [i-s, i) of that doubled list -- reproduced as the reference has it.
+void support_segs(const ChainCtx& k, int i, int b0, bool std, Seg* sg, int* n)
+{
+    const pc_topology& T = k.c->topo;
+    const size_t off = (size_t)b0 * k.HW * SLICE;
+    auto mu_tot = [&](int j) { return k.mut ? k.mut + (size_t)j * k.M * SLICE + off : k.mu + (size_t)(NS0 + j) * k.M * SLICE + off; };
+    auto sc = [&](int j) { return k.scale + (size_t)(NS0 + j) * k.M * SLICE + off; };
+    const int s = support_count(k.c, i);
+    for (int e = i - s; e < i; ++e) {
+        const float* p;
+        if (!std) p = mu_tot(e);
+        else if (!k.lik) p = T.support_std ? sc(e) : mu_tot(e);
+        else p = (e & 1) ? sc(e >> 1) : (T.support_std ? sc(e >> 1) : mu_tot(e >> 1));
+        sg[(*n)++] = {p, SLICE, SLICE};
+    }
+}
+
+// joiner_policy "cond" (CHProg_cnn.py:117-126,389-390): ye slot i = joiner[i](cat(enhanced, y_hat_base[i])) -- conv3x3 64->64, GELU,
+// conv3x3 64->64, GELU, conv3x3 64->32; the first reads the two 32-channel inputs as two segments, the last stores into ye (ld 320)
+int joiner(const ChainCtx& k, int i, int b0, int nb, const float* enhanced, hipStream_t st, const std::string& tag)
+{
+    pc_codec* c = k.c;
+    const size_t pi = (size_t)k.HW, m = (size_t)nb * pi;
+    float *ja, *jb;
+    PCCHK(c->buf("jn_a" + tag, m * 64, &ja));
+    PCCHK(c->buf("jn_b" + tag, m * 64, &jb));
+    const float* yb = img(k.yb, b0, pi * D0) + 32 * i;
+    float* ye = img(k.ye, b0, pi * D0) + 32 * i;
+    PCCHK(conv(st, c->joiner[i][0], {{enhanced, SLICE, SLICE}, {yb, D0, SLICE}}, nb, k.h, k.w, 1, ja, 64, PC_EPI_GELU));
+    PCCHK(conv(st, c->joiner[i][1], {{ja, 64, 64}}, nb, k.h, k.w, 1, jb, 64, PC_EPI_GELU));
+    return conv(st, c->joiner[i][2], {{jb, 64, 64}}, nb, k.h, k.w, 1, ye, D0, PC_EPI_NONE);
+}
+
+// the joiner's per-chain workspaces, created before any lane thread runs
+int joiner_workspace(pc_codec* c, const std::string& tag, size_t m)
+{
+    if (!c->topo.joiner_cond) return PC_OK;
+    float* d;
+    PCCHK(c->buf("jn_pm" + tag, m * SLICE, &d));
+    PCCHK(c->buf("jn_a" + tag, m * 64, &d));
+    return c->buf("jn_b" + tag, m * 64, &d);
+}
+
 // mean / scale stacks (+ quantile threshold) of chain step `step` (0..9 base, 10..19 enhancement) for images [b0, b0+nb), as one
 // grouped launch per layer: mean (z = 0) and scale (z = 1)
 int chain_params(const ChainCtx& k, int step, int b0, int nb, hipStream_t st, const std::string& tag)
@@ -1562,9 +1681,35 @@ int chain_params(const ChainCtx& k, int step, int b0, int nb, hipStream_t st, co
         const int i = step, ns = std::min(5, i);
         return stack5_pair(c, st, c->cc_mean[i], c->cc_scale[i], {{lm, MLAT, D0}, {yb, D0, 32 * ns}}, ls, nb, k.h, k.w, mu_i, sc_i, tm.c_str(), ts.c_str());
     }
-    const int i = step - NS0, s = std::min(5, i);
-    PCCHK(stack5_pair(c, st, c->cc_mean_p[i], c->cc_scale_p[i], {{lm + D0, MLAT, D0}, {yb + 32 * i, D0, 32}, {ye + 32 * (i - s), D0, 32 * s}},
-                      ls + D0, nb, k.h, k.w, mu_i, sc_i, tm.c_str(), ts.c_str()));
+    const int i = step - NS0;
+    const pc_topology& T = c->topo;
+    if (!T.all_scalable) {                      // support = the merged slices y_hat_slices_quality[i-s, i) (determine_support :377-383)
+        const int s = support_count(c, i);
+        PCCHK(stack5_pair(c, st, c->cc_mean_p[i], c->cc_scale_p[i], {{lm + D0, MLAT, D0}, {yb + 32 * i, D0, 32}, {ye + 32 * (i - s), D0, 32 * s}},
+                          ls + D0, nb, k.h, k.w, mu_i, sc_i, tm.c_str(), ts.c_str()));
+    } else {                                    // all_scalable (:784-785): mu_total / std_total entries, read in place from the per-step buffers
+        Seg sm[PC_MAX_SEG], ss[PC_MAX_SEG];
+        int nm = 0, ns = 0;
+        sm[nm++] = {lm + D0, MLAT, D0}; sm[nm++] = {yb + 32 * i, D0, 32};
+        ss[ns++] = {ls + D0, MLAT, D0}; ss[ns++] = {yb + 32 * i, D0, 32};
+        support_segs(k, i, b0, false, sm, &nm);
+        support_segs(k, i, b0, true, ss, &ns);
+        bool same = nm == ns;
+        for (int j = 2; same && j < nm; ++j) same = sm[j].p == ss[j].p;
+        if (same) {                             // std_total == mu_total (no support_std, compress / decompress): one grouped launch per layer
+            PCCHK(stack5_pair_n(c, st, c->cc_mean_p[i], c->cc_scale_p[i], sm, nm, ls + D0, nb, k.h, k.w, mu_i, sc_i, tm.c_str(), ts.c_str()));
+        } else {
+            PCCHK(stack5_n(c, st, c->cc_mean_p[i], sm, nm, nb, k.h, k.w, mu_i, SLICE, PC_EPI_NONE, tm.c_str()));
+            PCCHK(stack5_n(c, st, c->cc_scale_p[i], ss, ns, nb, k.h, k.w, sc_i, SLICE, PC_EPI_NONE, ts.c_str()));
+        }
+    }
+    if (k.mut) {                                // total_mu_rep: mut = mu + y_hat_base[i] (:800), the mean stack's last conv again with the
+                                                // residual epilogue -- the same conv value, one f32 add, as torch.add
+        float* t1;
+        PCCHK(c->buf(tm + "_t1", (size_t)nb * pi * 176, &t1));
+        PCCHK(conv(st, c->cc_mean_p[i].c[4], {{t1, 64, 64}}, nb, k.h, k.w, 1, k.mut + (size_t)i * k.M * SLICE + (size_t)b0 * pi * SLICE, SLICE,
+                   PC_EPI_RES, yb + 32 * i, D0));
+    }
     PCCHK(rem_refine(k, i, b0, nb, mu_i, sc_i, st, tag));                               // REM: refined scale before the mask (CHProgREM.py:812-826)
     if (k.mode == 1) PCCHK(mask_threshold(k, i, b0, nb, sc_i, st, tag));               // :819-824
     return PC_OK;
@@ -1584,9 +1729,29 @@ int chain_lrp(const ChainCtx& k, int step, int b0, int nb, hipStream_t sA, const
             return stack5(c, sA, c->lrp[i], {{lm, MLAT, D0}, {yb, D0, 32 * (i + 1)}}, nb, k.h, k.w, yb + 32 * i, D0, PC_EPI_LRP, yb + 32 * i, D0, nullptr, 0, tm.c_str());
         return stack5(c, sA, c->lrp[i], {{lm, MLAT, D0}, {yb, D0, 160}, {yb + 32 * i, D0, 32}}, nb, k.h, k.w, yb + 32 * i, D0, PC_EPI_LRP, yb + 32 * i, D0, nullptr, 0, tm.c_str());
     }
-    const int i = step - NS0, s = std::min(5, i);
-    return stack5(c, sA, c->lrp_p[i], {{lm + D0, MLAT, D0}, {yb + 32 * i, D0, 32}, {ye + 32 * (i - s), D0, 32 * (s + 1)}}, nb, k.h, k.w,
-                  ye + 32 * i, D0, PC_EPI_LRP_ADD, ye + 32 * i, D0, yb + 32 * i, D0, tm.c_str());
+    const int i = step - NS0;
+    const pc_topology& T = c->topo;
+    const bool rbl = T.residual_before_lrp && k.lik;          // forward only (:1153-1164): the slice is merged already
+    if (!T.all_scalable && !T.joiner_cond && !rbl) {          // the canonical form: LRP and merge "res" in one epilogue
+        const int s = support_count(c, i);
+        return stack5(c, sA, c->lrp_p[i], {{lm + D0, MLAT, D0}, {yb + 32 * i, D0, 32}, {ye + 32 * (i - s), D0, 32 * (s + 1)}}, nb, k.h, k.w,
+                      ye + 32 * i, D0, PC_EPI_LRP_ADD, ye + 32 * i, D0, yb + 32 * i, D0, tm.c_str());
+    }
+    // lrp_support = cat(mean_support, y_hat_slice) (:836-837); the slice sits in ye's slot i (merged already under rbl)
+    Seg sg[PC_MAX_SEG];
+    int n = 0;
+    sg[n++] = {lm + D0, MLAT, D0}; sg[n++] = {yb + 32 * i, D0, 32};
+    if (T.all_scalable) support_segs(k, i, b0, false, sg, &n);
+    else { const int s = support_count(c, i); if (s) sg[n++] = {ye + 32 * (i - s), D0, 32 * s}; }
+    sg[n++] = {ye + 32 * i, D0, 32};
+    if (rbl || !T.joiner_cond) {                              // LRP in place; "res" after it: the + base in the epilogue
+        return stack5_n(c, sA, c->lrp_p[i], sg, n, nb, k.h, k.w, ye + 32 * i, D0, rbl ? PC_EPI_LRP : PC_EPI_LRP_ADD, tm.c_str(), ye + 32 * i, D0,
+                        rbl ? nullptr : yb + 32 * i, D0);
+    }
+    float* pm;                                                // "cond": the enhanced slice, then the joiner into ye's slot
+    PCCHK(c->buf("jn_pm" + tag, (size_t)nb * pi * SLICE, &pm));
+    PCCHK(stack5_n(c, sA, c->lrp_p[i], sg, n, nb, k.h, k.w, pm, SLICE, PC_EPI_LRP, tm.c_str(), ye + 32 * i, D0));
+    return joiner(k, i, b0, nb, pm, sA, tag);
 }
 
 int encode_lane(const ChainCtx& k, int b0, int nb, hipStream_t sA, const std::string& tag)
@@ -1610,12 +1775,23 @@ int encode_lane(const ChainCtx& k, int b0, int nb, hipStream_t sA, const std::st
                               img(k.yb, b0, pi * D0) + 32 * step, D0, lik, lik_sb, sA));
         } else {                                                                         // enhancement slices, :775-845
             const int i = step - NS0;
+            const pc_topology& T = c->topo;
             float* m = k.masks ? k.masks + (size_t)i * k.M * SLICE + (size_t)b0 * pi * SLICE : nullptr;
+            // forward with residual_before_lrp (:1153-1154): "res" adds the base slice in the prep kernel, "cond" runs the joiner on the
+            // dequantised slice first; the LRP then refines the merged slice in place
+            const bool rbl = T.residual_before_lrp && k.lik;
+            float* yh = img(k.ye, b0, pi * D0) + 32 * i;
+            int ld_yh = D0;
+            if (rbl && T.joiner_cond) { PCCHK(c->buf("jn_pm" + tag, (size_t)nb * pi * SLICE, &yh)); ld_yh = SLICE; }
+            const float* yadd = (rbl && !T.joiner_cond) ? img(k.yb, b0, pi * D0) + 32 * i : nullptr;
             PCCHK(prep_encode(k.scale + so, SLICE, k.mu + so, SLICE, img(k.y, b0, pi * MLAT) + 32 * step, MLAT,
-                              img(k.y, b0, pi * MLAT) + 32 * i, MLAT, k.thr + (size_t)i * k.B + b0, k.mode, nb, k.HW,
+                              T.no_delta_encode ? nullptr : img(k.y, b0, pi * MLAT) + 32 * i, MLAT,       // delta_encode :780-781
+                              k.thr + (size_t)i * k.B + b0, k.mode, nb, k.HW,
                               c->scale_table, c->n_table, c->scale_bound, k.sym + so, k.idx + so, m,
-                              img(k.ye, b0, pi * D0) + 32 * i, D0, lik, lik_sb, sA,
-                              k.cust_map ? k.cust_map + ((size_t)b0 * D0 + (size_t)SLICE * i) * pi : nullptr, (int64_t)D0 * (int64_t)pi));
+                              yh, ld_yh, lik, lik_sb, sA,
+                              k.cust_map ? k.cust_map + ((size_t)b0 * D0 + (size_t)SLICE * i) * pi : nullptr, (int64_t)D0 * (int64_t)pi,
+                              yadd, D0));
+            if (rbl && T.joiner_cond) PCCHK(joiner(k, i, b0, nb, yh, sA, tag));
         }
         PCCHK(chain_lrp(k, step, b0, nb, sA, tag));
         if (k.sig) {
@@ -1691,6 +1867,7 @@ int run_chain(const ChainCtx& k, hipStream_t st, bool decode, const uint8_t* con
             PCCHK(c->buf(std::string(base) + std::to_string(g) + "_t0", m * 224, &dummy));
             PCCHK(c->buf(std::string(base) + std::to_string(g) + "_t1", m * 176, &dummy));
         }
+        PCCHK(joiner_workspace(c, std::to_string(g), m));
     }
     HIPCHK(hipEventRecord(c->eFork, st));
     for (int g = 0; g < nl; ++g) HIPCHK(hipStreamWaitEvent(c->lanes[g].sA, c->eFork, 0));     // every fallible fork step BEFORE a thread exists
@@ -1769,6 +1946,7 @@ int second_level_set(pc_codec* c, const ChainCtx& k, bool decoder, ChainCtx* k2)
     PCCHK(c->buf("yhat_enh_L2", k.M * D0, &k2->ye));
     PCCHK(c->buf("mu_L2", k.M * SLICE * 2 * NS0, &k2->mu));
     PCCHK(c->buf("scale_L2", k.M * SLICE * 2 * NS0, &k2->scale));
+    if (k.mut) PCCHK(c->buf("mut_L2", k.M * SLICE * NS0, &k2->mut));
     PCCHK(c->buf("thr_L2", (size_t)k.B * NS0, &k2->thr));
     PCCHK(c->buf("sym_L2", k.M * SLICE * 2 * NS0, &k2->sym));
     PCCHK(c->buf("idx_L2", k.M * SLICE * 2 * NS0, &k2->idx));
@@ -1788,6 +1966,7 @@ int ensure_pipeline(pc_codec* c, size_t M)
         PCCHK(c->buf(std::string(tag) + "_t0", M * 224, &dummy));
         PCCHK(c->buf(std::string(tag) + "_t1", M * 176, &dummy));
     }
+    for (const char* tag : {"PA", "PB"}) PCCHK(joiner_workspace(c, tag, M));
     return PC_OK;
 }
 
@@ -1807,6 +1986,7 @@ int chain_setup(pc_codec* c, CallKind kind, int B, int h, int w, ChainCtx* k)
     PCCHK(c->buf("yhat_enh", M * D0, &k->ye));
     PCCHK(c->buf("mu", M * SLICE * 2 * NS0, &k->mu));            // per-slice mu / scale kept for taps
     PCCHK(c->buf("scale", M * SLICE * 2 * NS0, &k->scale));
+    if (c->topo.total_mu_rep && c->topo.all_scalable) PCCHK(c->buf("mut", M * SLICE * NS0, &k->mut));   // mu_total is read only then
     PCCHK(c->buf("thr", (size_t)B * NS0, &k->thr));
     PCCHK(c->buf("sym", M * SLICE * 2 * NS0, &k->sym));
     PCCHK(c->buf("idx", M * SLICE * 2 * NS0, &k->idx));

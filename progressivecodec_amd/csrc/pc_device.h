@@ -132,6 +132,8 @@ struct pc_prep_params {
     uint8_t* idx8;                     // optional (decoder): the same indexes as bytes, [B][C][HW] -- what the host coder reads back
     float* mask;                       // [B][C][HW] float 0/1 or null
     float* yhat; int ld_yhat;          // NHWC: float(sym) + mu
+    const float* yadd; int ld_yadd;    // encoder, optional: yhat = (float(sym) + mu) + yadd -- the forward path's merge "res" before the
+                                       // LRP (residual_before_lrp, CHProg_cnn.py:1153-1154)
     float* lik; int64_t lik_sb;        // optional (encoder): Gaussian likelihood of the coded symbol, element (b, c, p) at
                                        // lik[b * lik_sb + c * HW + p]   (entropy_models.py:626-659)
 };

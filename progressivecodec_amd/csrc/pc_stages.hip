@@ -574,7 +574,9 @@ __global__ __launch_bounds__(256) void gc_prep_kernel(const pc_prep_params p)
             if (p.mask_mode != 0) v = v * m;
             const int32_t sym = (int32_t)pc_roundevenf(v);
             t_sym[c][px] = sym;
-            p.yhat[pix * p.ld_yhat + c] = (float)sym + mu;                 // CHProg_cnn.py:754-755,833-834
+            float yh = (float)sym + mu;                                    // CHProg_cnn.py:754-755,833-834
+            if (p.yadd) yh = yh + p.yadd[pix * p.ld_yadd + c];             // merge "res" before the LRP (:1153-1154)
+            p.yhat[pix * p.ld_yhat + c] = yh;
             if (p.lik) {                                                   // lower_bound_scale, then _likelihood
                 const float values = (p.mask_mode == 0) ? ((float)sym + mu) - mu : (float)sym;
                 t_lik[c][px] = gc_likelihood(values, sm > p.bound ? sm : p.bound);
@@ -637,11 +639,11 @@ __global__ __launch_bounds__(256) void gc_prep_vec_kernel(const pc_prep_params p
     pc_fill_table64(s_table, p.table, p.ntable);
     float thr = 0.0f;
     if (p.mask_mode == 1) thr = p.thr[b];
-    float4 s4[2], mu4[2], y4[2], yb4[2];
+    float4 s4[2], mu4[2], y4[2], yb4[2], ya4[2];
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
         const int u = tid + 256 * k, px = u >> 3, c0 = (u & 7) * 4;
-        s4[k] = mu4[k] = y4[k] = yb4[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+        s4[k] = mu4[k] = y4[k] = yb4[k] = ya4[k] = make_float4(0.f, 0.f, 0.f, 0.f);
         if (p0 + px < p.HW) {
             const int64_t pix = (int64_t)b * p.HW + p0 + px;
             s4[k] = *reinterpret_cast<const float4*>(p.scale + pix * p.ld_scale + c0);
@@ -649,6 +651,7 @@ __global__ __launch_bounds__(256) void gc_prep_vec_kernel(const pc_prep_params p
                 mu4[k] = *reinterpret_cast<const float4*>(p.mu + pix * p.ld_mu + c0);
                 y4[k] = *reinterpret_cast<const float4*>(p.y + pix * p.ld_y + c0);
                 if (p.ybase) yb4[k] = *reinterpret_cast<const float4*>(p.ybase + pix * p.ld_ybase + c0);
+                if (p.yadd) ya4[k] = *reinterpret_cast<const float4*>(p.yadd + pix * p.ld_yadd + c0);
             }
         }
     }
@@ -662,6 +665,7 @@ __global__ __launch_bounds__(256) void gc_prep_vec_kernel(const pc_prep_params p
         const float muv[4] = {mu4[k].x, mu4[k].y, mu4[k].z, mu4[k].w};
         const float yv[4] = {y4[k].x, y4[k].y, y4[k].z, y4[k].w};
         const float ybv[4] = {yb4[k].x, yb4[k].y, yb4[k].z, yb4[k].w};
+        const float yav[4] = {ya4[k].x, ya4[k].y, ya4[k].z, ya4[k].w};
         float yh[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -682,6 +686,7 @@ __global__ __launch_bounds__(256) void gc_prep_vec_kernel(const pc_prep_params p
                 const int32_t sym = (int32_t)pc_roundevenf(v);
                 t_sym[c][px] = sym;
                 yh[j] = (float)sym + mu;
+                if (p.yadd) yh[j] = yh[j] + yav[j];
                 if (LIK) {
                     const float values = (p.mask_mode == 0) ? ((float)sym + mu) - mu : (float)sym;
                     t_lik[c][px] = gc_likelihood(values, sm > p.bound ? sm : p.bound);
@@ -738,7 +743,7 @@ static bool prep_vec_ok(const pc_prep_params& p, int mode)   // mode 0 encoder, 
     bool ok = true;
     if (mode != 2) ok = ok && al16(p.scale) && !(p.ld_scale & 3) && al16(p.idx) && al16(p.mask) && (!p.idx8 || !(reinterpret_cast<uintptr_t>(p.idx8) & 3u));
     if (mode != 1) ok = ok && al16(p.mu) && !(p.ld_mu & 3) && al16(p.yhat) && !(p.ld_yhat & 3) && al16(p.sym);
-    if (mode == 0) ok = ok && al16(p.y) && !(p.ld_y & 3) && al16(p.ybase) && !(p.ld_ybase & 3) && al16(p.lik) && !(p.lik_sb & 3);
+    if (mode == 0) ok = ok && al16(p.y) && !(p.ld_y & 3) && al16(p.ybase) && !(p.ld_ybase & 3) && al16(p.yadd) && !(p.ld_yadd & 3) && al16(p.lik) && !(p.lik_sb & 3);
     return ok;
 }
 

@@ -244,14 +244,23 @@ class ChannelProgresssiveWACNN(_NativeCodecModule):
 
     def __init__(self, N=192, M=640, division_dimension=(320, 640), dim_chunk=32, multiple_decoder=True,
                  multiple_encoder=False, multiple_hyperprior=True, mask_policy="two-levels", lmbda_list=(0.0055, 0.04),
-                 joiner_policy="res", support_progressive_slices=5, delta_encode=True, u_net_post=0, device="cuda:0", **kwargs):
+                 joiner_policy="res", support_progressive_slices=5, delta_encode=True, u_net_post=0, residual_before_lrp=False,
+                 double_dim=False, support_std=False, total_mu_rep=False, all_scalable=False, device="cuda:0", **kwargs):
         super().__init__()
+        # the topology switches keep the reference's meaning (CHProg_cnn.py:29-49); the defaults here are the canonical topology
+        # (arch.CodecConfig), the reference's own constructor defaults differ (multiple_hyperprior=False, delta_encode=False,
+        # support_progressive_slices=0) -- pass them explicitly to build that model
         self.cfg = CodecConfig(N=N, M=M, division_dimension=tuple(division_dimension), dim_chunk=dim_chunk,
                                multiple_decoder=multiple_decoder, multiple_encoder=multiple_encoder,
-                               multiple_hyperprior=multiple_hyperprior, delta_encode=delta_encode,
+                               multiple_hyperprior=bool(multiple_hyperprior), delta_encode=bool(delta_encode),
                                joiner_policy=joiner_policy, support_progressive_slices=support_progressive_slices,
-                               mask_policy=mask_policy, u_net_post=u_net_post)
+                               mask_policy=mask_policy, u_net_post=u_net_post, all_scalable=bool(all_scalable),
+                               total_mu_rep=bool(total_mu_rep), support_std=bool(support_std),
+                               residual_before_lrp=bool(residual_before_lrp), double_dim=bool(double_dim))
         self.cfg.check_supported()
+        self.multiple_hyperprior, self.delta_encode, self.joiner_policy = self.cfg.multiple_hyperprior, self.cfg.delta_encode, joiner_policy
+        self.support_progressive_slices, self.all_scalable, self.total_mu_rep = support_progressive_slices, self.cfg.all_scalable, self.cfg.total_mu_rep
+        self.support_std, self.residual_before_lrp, self.double_dim = self.cfg.support_std, self.cfg.residual_before_lrp, self.cfg.double_dim
         self.u_net_post = u_net_post
         self.mask_policy = mask_policy
         self.lmbda_list = list(lmbda_list)
@@ -262,6 +271,9 @@ class ChannelProgresssiveWACNN(_NativeCodecModule):
 
     def _configure_native(self):
         check(lib().pc_codec_set_post_filter(self._h, self.cfg.u_net_post), "pc_codec_set_post_filter")
+        if not self.cfg.canonical_topology:                                       # the object's default is the canonical topology
+            t = (C.c_int * 8)(*self.cfg.topology())
+            check(lib().pc_codec_set_topology(self._h, C.cast(t, C.c_void_p)), "pc_codec_set_topology")
 
     def forward(self, *args, **kwargs):
         raise NotImplementedError("training forward() (CHProg_cnn.py:478-682) is out of scope; use forward_single_quality() for rate estimation")

@@ -85,7 +85,10 @@ class CodecPipeline:
                                 multiple_decoder=_encoder.cfg.multiple_decoder, multiple_encoder=_encoder.cfg.multiple_encoder,
                                 multiple_hyperprior=_encoder.cfg.multiple_hyperprior, mask_policy=_encoder.mask_policy,
                                 joiner_policy=_encoder.cfg.joiner_policy, support_progressive_slices=_encoder.cfg.support_progressive_slices,
-                                delta_encode=_encoder.cfg.delta_encode, u_net_post=_encoder.cfg.u_net_post)
+                                delta_encode=_encoder.cfg.delta_encode, u_net_post=_encoder.cfg.u_net_post,
+                                all_scalable=_encoder.cfg.all_scalable, total_mu_rep=_encoder.cfg.total_mu_rep,
+                                support_std=_encoder.cfg.support_std, residual_before_lrp=_encoder.cfg.residual_before_lrp,
+                                double_dim=_encoder.cfg.double_dim)
         else:
             if state_dict is None:
                 raise ValueError("CodecPipeline needs a state dict (or use CodecPipeline.from_model)")

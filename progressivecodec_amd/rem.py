@@ -29,6 +29,9 @@ class PostRateProcessedNetwork(_module_base()):
         super().__init__()
         if not isinstance(base_net, ChannelProgresssiveWACNN):
             raise AssertionError("base_net must be a ChannelProgresssiveWACNN")               # CHProgREM.py:224
+        if not base_net.cfg.canonical_topology:
+            # the REM reads the topology switches too (CHProgREM.py:561-589,785-883); only the canonical base is implemented
+            raise NotImplementedError("PostRateProcessedNetwork over a base net with a non-canonical topology (%r)" % (base_net.cfg,))
         if not 1 <= len(check_levels) <= 3:
             raise ValueError("one to three check levels")
         self.base_net = base_net
