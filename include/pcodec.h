@@ -411,6 +411,89 @@ typedef struct pc_test_conv_desc {
 #define PC_FORM_IN_GDN 7                   /* fused input-layer GDN */
 PC_API int pc_test_conv(const pc_test_conv_desc* d, int* plan, void* stream);
 
+/* Test aid: one launch of a non-conv stage launcher (progressivecodec_amd/csrc/pc_stages.hip; GDN: the codec's own gdn()) from a plain
+ * descriptor that carries the union of the launchers' arguments, the ones the wrappers above hide included (lik / lik_sb, mask_src /
+ * mask_sb, yadd / ld_yadd, idx8, bias_ji, the quantile's batch stride and scratch, mu / ld_mu of the REM combine).  `size` must be
+ * sizeof(pc_test_stage_desc): a mismatch returns PC_ERR_ARG before anything else is read.  Fields by kind:
+ *   PREP_ENC / PREP_DEC_INDEX / PREP_DEQUANT   the pc_gc_prep_* arguments under their own names (B, HW; C must be 32)
+ *   ATTENTION   x = qkv, aux0 = bias ([heads][T][T], bias_ji = 1: stored [h][j][i]), B H W C heads ws shift fscale, out
+ *   GDN         x, aux0 = beta, aux1 = gamma [C_out][C_in], B H W C inverse, out
+ *   QUANTILE    scale ld_scale B HW C q, out = thr [B], work (NULL: allocated by the launcher), sb (0: HW * ld_scale)
+ *   EB_QUANT    x = z, aux0 = medians, B HW C, sym, out = zhat;   EB_DEQUANT  sym, aux0, out;   EB_LIK  sym, aux0, aux1 = net, out = lik
+ *   REM         x = ret, ld_x, out = scale (updated in place), ld_scale, B HW, thr / mode_star, thr_bar / mode_bar, out2 = mu (or NULL), ld_mu
+ *   NCHW_SLICE  x = src, sb = batch stride, B HW C, out
+ *   SE          x, aux0 = fc1, aux1 = fc2, B HW C, out2 = part, out = s;   MAXPOOL  x, B H W C, out
+ * plan (optional, 1 int): the kernel variant the launcher chose (PC_SPLAN_*), reported by the launcher itself.
+ * Returns PC_ERR_ARG for every launch a launcher refuses (nothing is launched then).  Asynchronous on `stream`. */
+typedef struct pc_test_stage_desc {
+    int size;
+    int kind;
+    int B;
+    int HW;
+    int C;
+    int H;
+    int W;
+    const float* scale;
+    int ld_scale;
+    const float* mu;
+    int ld_mu;
+    const float* y;
+    int ld_y;
+    const float* ybase;
+    int ld_ybase;
+    const float* yadd;
+    int ld_yadd;
+    const float* thr;
+    int mask_mode;
+    const float* mask_src;
+    int64_t mask_sb;
+    const float* table;
+    int ntable;
+    float bound;
+    int32_t* sym;
+    int32_t* idx;
+    uint8_t* idx8;
+    float* mask;
+    float* yhat;
+    int ld_yhat;
+    float* lik;
+    int64_t lik_sb;
+    const float* x;
+    int ld_x;
+    const float* aux0;
+    const float* aux1;
+    float* out;
+    float* out2;
+    int heads;
+    int ws;
+    int shift;
+    int bias_ji;
+    float fscale;
+    int inverse;
+    float q;
+    uint32_t* work;
+    int64_t sb;
+    const float* thr_bar;
+    int mode_star;
+    int mode_bar;
+} pc_test_stage_desc;
+enum { PC_STAGE_PREP_ENC = 1, PC_STAGE_PREP_DEC_INDEX = 2, PC_STAGE_PREP_DEQUANT = 3, PC_STAGE_ATTENTION = 4, PC_STAGE_GDN = 5,
+       PC_STAGE_QUANTILE = 6, PC_STAGE_EB_QUANT = 7, PC_STAGE_EB_DEQUANT = 8, PC_STAGE_EB_LIK = 9, PC_STAGE_REM = 10,
+       PC_STAGE_NCHW_SLICE = 11, PC_STAGE_SE = 12, PC_STAGE_MAXPOOL = 13 };
+#define PC_SPLAN_SINGLE 1                  /* a launcher with one kernel (eb_*, rem_combine, nchw slice, SE squeeze, maxpool) */
+#define PC_SPLAN_PREP_SCALAR 2             /* gc_prep_kernel / gc_dequant_kernel */
+#define PC_SPLAN_PREP_VEC 3                /* gc_prep_vec_kernel<., false> / gc_dequant_vec_kernel */
+#define PC_SPLAN_PREP_VEC_LIK 4            /* gc_prep_vec_kernel<0, true> */
+#define PC_SPLAN_ATT_8_24 5                /* win_attention_kernel<8, 24> */
+#define PC_SPLAN_ATT_4_80 6
+#define PC_SPLAN_ATT_4_40 7
+#define PC_SPLAN_Q_REG8 8                  /* quantile_thr_kernel<8>: n <= 8192 */
+#define PC_SPLAN_Q_REG32 9                 /* quantile_thr_kernel<32>: n <= PC_QUANTILE_SMALL_N */
+#define PC_SPLAN_Q_MULTI_VEC 10            /* sample -> bracket<true> -> final */
+#define PC_SPLAN_Q_MULTI_SCALAR 11         /* sample -> bracket<false> -> final */
+#define PC_SPLAN_GDN 16                    /* + the conv launcher's PC_PLAN_* of the GDN launch */
+PC_API int pc_test_stage(const pc_test_stage_desc* d, int* plan, void* stream);
+
 /* Debug/test taps: copy an internal device tensor of the last call to host ("y", "z", "latent_means", ...). */
 PC_API int pc_codec_read_tap(pc_codec* c, const char* name, float* host_out, size_t cap_floats, size_t* n_floats);
 PC_API int pc_codec_read_tap_i32(pc_codec* c, const char* name, int32_t* host_out, size_t cap, size_t* n);

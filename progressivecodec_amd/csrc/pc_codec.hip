@@ -166,12 +166,12 @@ struct pc_codec {
 namespace {
 
 // conv launch, optionally bracketed by HIP events on the launch stream (profile mode)
-int launch_conv(const pc_conv_params& q_in, hipStream_t st)
+int launch_conv(const pc_conv_params& q_in, hipStream_t st, int* plan = nullptr)
 {
     pc_conv_params q = q_in;
     q.rowtab_cache = g_rowtabs;
     pc_codec* c = g_prof;
-    if (!c) return pc_conv_launch(q, st);
+    if (!c) return pc_conv_launch(q, st, plan);
     long taps = 0;
     for (int ph = 0; ph < q.nphase; ++ph) taps += q.ntap[ph];
     const double ng = q.ngroup == 2 ? 2.0 : 1.0;
@@ -200,7 +200,7 @@ int launch_conv(const pc_conv_params& q_in, hipStream_t st)
         e0 = c->ev[c->ev_used++]; e1 = c->ev[c->ev_used++];
     }
     HIPCHK(hipEventRecord(e0, st));
-    const int r = pc_conv_launch(q, st);
+    const int r = pc_conv_launch(q, st, plan);
     HIPCHK(hipEventRecord(e1, st));
     return r;
 }
@@ -497,7 +497,7 @@ int conv(hipStream_t st, const ConvW& w, std::initializer_list<Seg> segs, int B,
     return conv_n(st, w, segs.begin(), (int)segs.size(), B, H, W, stride, out, ldo, epi, aux0, ld0, aux1, ld1, pixel_shuffle, g1, out_relu);
 }
 
-int gdn(hipStream_t st, const GdnW& g, const float* x, int B, int H, int W, bool inverse, float* out)
+int gdn(hipStream_t st, const GdnW& g, const float* x, int B, int H, int W, bool inverse, float* out, int* plan = nullptr)
 {
     pc_conv_params q;
     std::memset(&q, 0, sizeof(q));
@@ -508,7 +508,7 @@ int gdn(hipStream_t st, const GdnW& g, const float* x, int B, int H, int W, bool
     q.Ho = H; q.Wo = W; q.outH = H; q.outW = W; q.M = B * H * W;
     q.out = out; q.out_sc = 1; q.out_sx = g.C; q.out_sy = (int64_t)W * g.C; q.out_sb = (int64_t)H * W * g.C;
     q.epi = inverse ? PC_EPI_IGDN : PC_EPI_GDN; q.aux0 = x; q.ld0 = g.C;
-    return launch_conv(q, st);
+    return launch_conv(q, st, plan);
 }
 
 // ResidualUnit (layers/layers.py:38-57): x -> gelu(conv1x1) -> gelu(conv3x3) -> conv1x1 + x -> gelu
@@ -968,6 +968,73 @@ extern "C" int pc_test_conv(const pc_test_conv_desc* d, int* plan, void* stream)
     q.out_relu = d->out_relu;
     if (d->ngroup == 2) { q.ngroup = 2; q.g1_seg0 = d->g1_seg0; q.g1_w = d->g1_w; q.g1_bias = d->g1_bias; q.g1_out = d->g1_out; }
     return pc_conv_launch(q, (hipStream_t)stream, plan);
+}
+
+extern "C" int pc_test_stage(const pc_test_stage_desc* d, int* plan, void* stream)
+{
+    if (plan) plan[0] = 0;
+    if (!d || d->size != (int)sizeof(pc_test_stage_desc)) return PC_ERR_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    int chosen = 0, rc = PC_ERR_ARG;
+    switch (d->kind) {
+    case PC_STAGE_PREP_ENC: case PC_STAGE_PREP_DEC_INDEX: case PC_STAGE_PREP_DEQUANT: {
+        pc_prep_params p;
+        std::memset(&p, 0, sizeof(p));
+        p.B = d->B; p.HW = d->HW; p.C = d->C;
+        p.scale = d->scale; p.ld_scale = d->ld_scale; p.mu = d->mu; p.ld_mu = d->ld_mu; p.y = d->y; p.ld_y = d->ld_y;
+        p.ybase = d->ybase; p.ld_ybase = d->ld_ybase; p.yadd = d->yadd; p.ld_yadd = d->ld_yadd;
+        p.thr = d->thr; p.mask_mode = d->mask_mode; p.mask_src = d->mask_src; p.mask_sb = d->mask_sb;
+        p.table = d->table; p.ntable = d->ntable; p.bound = d->bound;
+        p.sym = d->sym; p.idx = d->idx; p.idx8 = d->idx8; p.mask = d->mask; p.yhat = d->yhat; p.ld_yhat = d->ld_yhat;
+        p.lik = d->lik; p.lik_sb = d->lik_sb;
+        if (d->kind == PC_STAGE_PREP_ENC) {
+            if (!p.scale || !p.mu || !p.y || !p.sym || !p.idx || !p.yhat || !p.table || (p.mask_mode == 1 && !p.thr)) return PC_ERR_ARG;
+            rc = pc_prep_enc_launch(p, st, &chosen);
+        } else if (d->kind == PC_STAGE_PREP_DEC_INDEX) {
+            if (!p.scale || !p.idx || !p.table || (p.mask_mode == 1 && !p.thr)) return PC_ERR_ARG;
+            rc = pc_prep_dec_index_launch(p, st, &chosen);
+        } else {
+            if (!p.sym || !p.mu || !p.yhat) return PC_ERR_ARG;
+            rc = pc_prep_dec_dequant_launch(p, st, &chosen);
+        }
+        break;
+    }
+    case PC_STAGE_ATTENTION:
+        rc = pc_win_attention_launch(d->x, d->aux0, d->B, d->H, d->W, d->C, d->heads, d->ws, d->shift, d->fscale, d->out, st, d->bias_ji, &chosen);
+        break;
+    case PC_STAGE_GDN: {
+        if (!d->x || !d->aux0 || !d->aux1 || !d->out || d->C <= 0 || d->C % 16 || d->B <= 0 || d->H <= 0 || d->W <= 0) return PC_ERR_ARG;
+        GdnW g; g.beta = const_cast<float*>(d->aux0); g.gamma = const_cast<float*>(d->aux1); g.C = d->C;
+        int cp[2] = {0, 0};
+        rc = gdn(st, g, d->x, d->B, d->H, d->W, d->inverse != 0, d->out, cp);
+        chosen = PC_SPLAN_GDN + cp[0];
+        break;
+    }
+    case PC_STAGE_QUANTILE:
+        if (!d->scale || !d->out) return PC_ERR_ARG;
+        rc = pc_quantile_thr_launch(d->scale, d->ld_scale, d->B, d->HW, d->C, d->q, d->out, d->work, st, d->sb, &chosen);
+        break;
+    case PC_STAGE_EB_QUANT:
+        rc = pc_eb_quant_launch(d->x, d->B, d->HW, d->C, d->aux0, d->sym, d->out, st); chosen = PC_SPLAN_SINGLE; break;
+    case PC_STAGE_EB_DEQUANT:
+        rc = pc_eb_dequant_launch(d->sym, d->B, d->HW, d->C, d->aux0, d->out, st); chosen = PC_SPLAN_SINGLE; break;
+    case PC_STAGE_EB_LIK:
+        rc = pc_eb_likelihood_launch(d->sym, d->B, d->HW, d->C, d->aux0, d->aux1, d->out, st); chosen = PC_SPLAN_SINGLE; break;
+    case PC_STAGE_REM:
+        if ((d->out2 && d->ld_mu <= 0) || d->ld_x <= 0 || d->ld_scale <= 0) return PC_ERR_ARG;
+        rc = pc_rem_combine_launch(d->x, d->ld_x, d->out, d->ld_scale, d->B, d->HW, d->thr, d->mode_star, d->thr_bar, d->mode_bar, st, d->out2, d->ld_mu);
+        chosen = PC_SPLAN_SINGLE; break;
+    case PC_STAGE_NCHW_SLICE:
+        rc = pc_nchw_slice_to_nhwc_launch(d->x, d->sb, d->B, d->HW, d->C, d->out, st); chosen = PC_SPLAN_SINGLE; break;
+    case PC_STAGE_SE:
+        rc = pc_se_squeeze_launch(d->x, d->B, d->HW, d->C, d->aux0, d->aux1, d->out2, d->out, st); chosen = PC_SPLAN_SINGLE; break;
+    case PC_STAGE_MAXPOOL:
+        rc = pc_maxpool2_launch(d->x, d->B, d->H, d->W, d->C, d->out, st); chosen = PC_SPLAN_SINGLE; break;
+    default:
+        return PC_ERR_ARG;
+    }
+    if (plan && rc == PC_OK) plan[0] = chosen;
+    return rc;
 }
 
 extern "C" int pc_gdn_nhwc(const float* x, int B, int H, int W, int C, const float* beta, const float* gamma, int inverse,

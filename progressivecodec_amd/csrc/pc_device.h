@@ -109,11 +109,12 @@ size_t pc_rowtab_cache_bytes(pc_rowtab_cache* c);
 // weight layout the launcher expects for a layer (kind 0 conv / 1 transposed conv k5 s2)
 int pc_conv_weight_layout(int kind, int Cin, int Cout, int k);
 
+// `plan` (optional, host side) of the stage launchers below: the kernel variant chosen (PC_SPLAN_*, include/pcodec.h)
 // window attention core
 // bias: dense relative-position bias, [heads][T][T] as bias[h][i][j] (bias_ji = 0: the module's order, win_attention.py:97-100) or
 // transposed bias[h][j][i] (bias_ji = 1: what the codec stores -- coalesced across the query lanes)
 int pc_win_attention_launch(const float* qkv, const float* bias, int B, int H, int W, int C, int heads, int ws,
-                            int shift, float scale, float* out, hipStream_t stream, int bias_ji = 0);
+                            int shift, float scale, float* out, hipStream_t stream, int bias_ji = 0, int* plan = nullptr);
 
 // entropy-parameter stages
 struct pc_prep_params {
@@ -137,12 +138,12 @@ struct pc_prep_params {
     float* lik; int64_t lik_sb;        // optional (encoder): Gaussian likelihood of the coded symbol, element (b, c, p) at
                                        // lik[b * lik_sb + c * HW + p]   (entropy_models.py:626-659)
 };
-int pc_prep_enc_launch(const pc_prep_params& p, hipStream_t stream);
-int pc_prep_dec_index_launch(const pc_prep_params& p, hipStream_t stream);   // scale(+mask) -> idx (+mask)
-int pc_prep_dec_dequant_launch(const pc_prep_params& p, hipStream_t stream); // sym + mu -> yhat
+int pc_prep_enc_launch(const pc_prep_params& p, hipStream_t stream, int* plan = nullptr);
+int pc_prep_dec_index_launch(const pc_prep_params& p, hipStream_t stream, int* plan = nullptr);   // scale(+mask) -> idx (+mask)
+int pc_prep_dec_dequant_launch(const pc_prep_params& p, hipStream_t stream, int* plan = nullptr); // sym + mu -> yhat
 
 int pc_quantile_thr_launch(const float* scale, int ld, int B, int HW, int C, float q, float* thr, uint32_t* work,
-                           hipStream_t stream, int64_t batch_stride = 0);   // batch_stride 0: HW * ld
+                           hipStream_t stream, int64_t batch_stride = 0, int* plan = nullptr);   // batch_stride 0: HW * ld
 size_t pc_quantile_work_bytes(int B);
 #define PC_QUANTILE_SMALL_N 32768   // up to here one workgroup per image holds the keys in registers and `work` is not used
 

@@ -814,21 +814,26 @@ __global__ void nchw_slice_to_nhwc_kernel(const float* __restrict__ src, int64_t
 #define PC_LAUNCH_CHECK() (hipGetLastError() == hipSuccess ? PC_OK : PC_ERR_HIP)
 
 int pc_win_attention_launch(const float* qkv, const float* bias, int B, int H, int W, int C, int heads, int ws,
-                            int shift, float scale, float* out, hipStream_t stream, int bias_ji)
+                            int shift, float scale, float* out, hipStream_t stream, int bias_ji, int* plan)
 {
-    if (heads <= 0 || C % heads || H % ws || W % ws || shift < 0 || shift >= ws) return PC_ERR_ARG;
+    if (!qkv || !bias || !out || B <= 0 || H <= 0 || W <= 0 || ws <= 0 || heads <= 0 || C % heads || H % ws || W % ws || shift < 0 || shift >= ws) return PC_ERR_ARG;
     const int d = C / heads, T = ws * ws;
     const int npairs = B * (H / ws) * (W / ws) * heads;
     const int per_block = 4 * (64 / T);
     dim3 grid((npairs + per_block - 1) / per_block), block(256);
-    if (ws == 8 && d == 24)
+    int chosen;
+    if (ws == 8 && d == 24) {
+        chosen = PC_SPLAN_ATT_8_24;
         hipLaunchKernelGGL((win_attention_kernel<8, 24>), grid, block, 0, stream, qkv, bias, B, H, W, C, heads, shift, scale, out, npairs, bias_ji);
-    else if (ws == 4 && d == 80)
+    } else if (ws == 4 && d == 80) {
+        chosen = PC_SPLAN_ATT_4_80;
         hipLaunchKernelGGL((win_attention_kernel<4, 80>), grid, block, 0, stream, qkv, bias, B, H, W, C, heads, shift, scale, out, npairs, bias_ji);
-    else if (ws == 4 && d == 40)
+    } else if (ws == 4 && d == 40) {
+        chosen = PC_SPLAN_ATT_4_40;
         hipLaunchKernelGGL((win_attention_kernel<4, 40>), grid, block, 0, stream, qkv, bias, B, H, W, C, heads, shift, scale, out, npairs, bias_ji);
-    else
+    } else
         return PC_ERR_ARG;
+    if (plan) *plan = chosen;
     return PC_LAUNCH_CHECK();
 }
 
@@ -878,19 +883,21 @@ __global__ void eb_likelihood_kernel(const int32_t* __restrict__ sym, int B, int
 
 int pc_eb_likelihood_launch(const int32_t* sym, int B, int HW, int C, const float* med, const float* net, float* lik, hipStream_t stream)
 {
+    if (!sym || !med || !net || !lik || B <= 0 || HW <= 0 || C <= 0) return PC_ERR_ARG;
     const int64_t n = (int64_t)B * HW * C;
     const int blocks = (int)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048);
     hipLaunchKernelGGL(eb_likelihood_kernel, dim3(blocks), dim3(256), 0, stream, sym, B, HW, C, med, net, lik);
     return PC_LAUNCH_CHECK();
 }
 
-int pc_quantile_thr_launch(const float* scale, int ld, int B, int HW, int C, float q, float* thr, uint32_t* work, hipStream_t stream, int64_t sb)
+int pc_quantile_thr_launch(const float* scale, int ld, int B, int HW, int C, float q, float* thr, uint32_t* work, hipStream_t stream, int64_t sb, int* plan)
 {
     if (B <= 0 || HW <= 0 || C <= 0) return PC_ERR_ARG;
     if (sb == 0) sb = (int64_t)HW * ld;
     const int64_t n = (int64_t)HW * C;
-    if (n <= 1024 * 8) hipLaunchKernelGGL(quantile_thr_kernel<8>, dim3(B), dim3(1024), 0, stream, scale, ld, HW, C, q, thr, sb);
-    else if (n <= PC_QUANTILE_SMALL_N) hipLaunchKernelGGL(quantile_thr_kernel<32>, dim3(B), dim3(1024), 0, stream, scale, ld, HW, C, q, thr, sb);
+    int chosen;
+    if (n <= 1024 * 8) { chosen = PC_SPLAN_Q_REG8; hipLaunchKernelGGL(quantile_thr_kernel<8>, dim3(B), dim3(1024), 0, stream, scale, ld, HW, C, q, thr, sb); }
+    else if (n <= PC_QUANTILE_SMALL_N) { chosen = PC_SPLAN_Q_REG32; hipLaunchKernelGGL(quantile_thr_kernel<32>, dim3(B), dim3(1024), 0, stream, scale, ld, HW, C, q, thr, sb); }
     else {
         uint32_t* w = work;
         if (!w && hipMallocAsync(reinterpret_cast<void**>(&w), pc_quantile_work_bytes(B), stream) != hipSuccess) return PC_ERR_HIP;
@@ -901,38 +908,47 @@ int pc_quantile_thr_launch(const float* scale, int ld, int B, int HW, int C, flo
         else hipLaunchKernelGGL(quantile_bracket_kernel<false>, dim3(G, B), dim3(256), 0, stream, scale, ld, HW, C, sb, w);
         hipLaunchKernelGGL(quantile_final_kernel, dim3(B), dim3(1024), 0, stream, scale, ld, HW, C, q, thr, sb, (const uint32_t*)w);
         if (!work && hipFreeAsync(w, stream) != hipSuccess) return PC_ERR_HIP;
+        chosen = vec ? PC_SPLAN_Q_MULTI_VEC : PC_SPLAN_Q_MULTI_SCALAR;
     }
+    if (plan) *plan = chosen;
     return PC_LAUNCH_CHECK();
 }
 size_t pc_quantile_work_bytes(int B) { return (size_t)B * PC_QW_STRIDE * sizeof(uint32_t); }
 
-int pc_prep_enc_launch(const pc_prep_params& p, hipStream_t stream)
+int pc_prep_enc_launch(const pc_prep_params& p, hipStream_t stream, int* plan)
 {
-    if (p.C != 32 || p.ntable > 64 || p.ntable < 2) return PC_ERR_ARG;
+    if (p.C != 32 || p.ntable > 64 || p.ntable < 2 || p.B <= 0 || p.HW <= 0) return PC_ERR_ARG;
     const dim3 grid((p.HW + 63) / 64, p.B);
-    if (!prep_vec_ok(p, 0)) hipLaunchKernelGGL((gc_prep_kernel<0>), grid, dim3(256), 0, stream, p);
-    else if (p.lik) hipLaunchKernelGGL((gc_prep_vec_kernel<0, true>), grid, dim3(256), 0, stream, p);
-    else hipLaunchKernelGGL((gc_prep_vec_kernel<0, false>), grid, dim3(256), 0, stream, p);
+    int chosen;
+    if (!prep_vec_ok(p, 0)) { chosen = PC_SPLAN_PREP_SCALAR; hipLaunchKernelGGL((gc_prep_kernel<0>), grid, dim3(256), 0, stream, p); }
+    else if (p.lik) { chosen = PC_SPLAN_PREP_VEC_LIK; hipLaunchKernelGGL((gc_prep_vec_kernel<0, true>), grid, dim3(256), 0, stream, p); }
+    else { chosen = PC_SPLAN_PREP_VEC; hipLaunchKernelGGL((gc_prep_vec_kernel<0, false>), grid, dim3(256), 0, stream, p); }
+    if (plan) *plan = chosen;
     return PC_LAUNCH_CHECK();
 }
-int pc_prep_dec_index_launch(const pc_prep_params& p, hipStream_t stream)
+int pc_prep_dec_index_launch(const pc_prep_params& p, hipStream_t stream, int* plan)
 {
-    if (p.C != 32 || p.ntable > 64 || p.ntable < 2) return PC_ERR_ARG;
+    if (p.C != 32 || p.ntable > 64 || p.ntable < 2 || p.B <= 0 || p.HW <= 0) return PC_ERR_ARG;
     const dim3 grid((p.HW + 63) / 64, p.B);
-    if (!prep_vec_ok(p, 1)) hipLaunchKernelGGL((gc_prep_kernel<1>), grid, dim3(256), 0, stream, p);
+    const bool vec = prep_vec_ok(p, 1);
+    if (!vec) hipLaunchKernelGGL((gc_prep_kernel<1>), grid, dim3(256), 0, stream, p);
     else hipLaunchKernelGGL((gc_prep_vec_kernel<1, false>), grid, dim3(256), 0, stream, p);
+    if (plan) *plan = vec ? PC_SPLAN_PREP_VEC : PC_SPLAN_PREP_SCALAR;
     return PC_LAUNCH_CHECK();
 }
-int pc_prep_dec_dequant_launch(const pc_prep_params& p, hipStream_t stream)
+int pc_prep_dec_dequant_launch(const pc_prep_params& p, hipStream_t stream, int* plan)
 {
-    if (p.C != 32) return PC_ERR_ARG;
+    if (p.C != 32 || p.B <= 0 || p.HW <= 0) return PC_ERR_ARG;
     const dim3 grid((p.HW + 63) / 64, p.B);
-    if (!prep_vec_ok(p, 2)) hipLaunchKernelGGL(gc_dequant_kernel, grid, dim3(256), 0, stream, p);
+    const bool vec = prep_vec_ok(p, 2);
+    if (!vec) hipLaunchKernelGGL(gc_dequant_kernel, grid, dim3(256), 0, stream, p);
     else hipLaunchKernelGGL(gc_dequant_vec_kernel, grid, dim3(256), 0, stream, p);
+    if (plan) *plan = vec ? PC_SPLAN_PREP_VEC : PC_SPLAN_PREP_SCALAR;
     return PC_LAUNCH_CHECK();
 }
 int pc_eb_quant_launch(const float* z, int B, int HW, int C, const float* med, int32_t* sym, float* zhat, hipStream_t stream)
 {
+    if (!z || !med || !sym || !zhat || B <= 0 || HW <= 0 || C <= 0) return PC_ERR_ARG;
     const int64_t n = (int64_t)B * HW * C;
     const int blocks = (int)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048);
     hipLaunchKernelGGL(eb_quant_kernel, dim3(blocks), dim3(256), 0, stream, z, B, HW, C, med, sym, zhat);
@@ -940,6 +956,7 @@ int pc_eb_quant_launch(const float* z, int B, int HW, int C, const float* med, i
 }
 int pc_eb_dequant_launch(const int32_t* sym, int B, int HW, int C, const float* med, float* zhat, hipStream_t stream)
 {
+    if (!sym || !med || !zhat || B <= 0 || HW <= 0 || C <= 0) return PC_ERR_ARG;
     const int64_t n = (int64_t)B * HW * C;
     const int blocks = (int)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048);
     hipLaunchKernelGGL(eb_dequant_kernel, dim3(blocks), dim3(256), 0, stream, sym, B, HW, C, med, zhat);
