@@ -165,6 +165,20 @@ struct pc_codec {
 
 namespace {
 
+// The launch state (g_prof, g_rowtabs) of this thread while it works for codec `c` (null: for none): set here, put back when the scope
+// ends -- null on a thread that was not already inside a call, so a stand-alone entry point (pc_gdn_nhwc, pc_test_stage) never sees a
+// codec's cache or profile.
+struct LaunchState {
+    pc_codec* prof0;
+    pc_rowtab_cache* rowtabs0;
+    explicit LaunchState(pc_codec* c) : prof0(g_prof), rowtabs0(g_rowtabs) { g_prof = c && c->profile ? c : nullptr; g_rowtabs = c ? c->rowtabs : nullptr; }
+    ~LaunchState() { g_prof = prof0; g_rowtabs = rowtabs0; }
+    LaunchState(const LaunchState&) = delete;
+    LaunchState& operator=(const LaunchState&) = delete;
+};
+
+double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
 // conv launch, optionally bracketed by HIP events on the launch stream (profile mode)
 int launch_conv(const pc_conv_params& q_in, hipStream_t st, int* plan = nullptr)
 {
@@ -449,6 +463,28 @@ void fill_deconv_taps(pc_conv_params& q)   // ConvTranspose2d(5, s2, p2, op1) as
         }
 }
 
+// Tap table and geometry (B, H, W, Ho, Wo, outH, outW, M, pixel_shuffle) of one launch.  kind 0: Conv2d(k, stride, padding k/2);
+// 1: ConvTranspose2d(5, s2, p2, op1); 2: the sub-pixel output layer, which always stores through the PixelShuffle epilogue.
+int conv_geometry(pc_conv_params& q, int kind, int k, int stride, int H, int W, int B, bool pixel_shuffle)
+{
+    if (B <= 0 || H <= 0 || W <= 0) return PC_ERR_ARG;
+    q.B = B; q.H = H; q.W = W;
+    q.Ho = H; q.Wo = W;
+    if (kind == 0) {
+        if (k <= 0 || k > 5 || stride <= 0) return PC_ERR_ARG;
+        fill_conv_taps(q, k, stride);
+        q.Ho = (H + 2 * (k / 2) - k) / stride + 1;
+        q.Wo = (W + 2 * (k / 2) - k) / stride + 1;
+    } else if (kind == 1) fill_deconv_taps(q);
+    else if (kind == 2) fill_subpixel_taps(q);
+    else return PC_ERR_ARG;
+    q.outH = q.osy * q.Ho; q.outW = q.osx * q.Wo;
+    q.M = B * q.Ho * q.Wo;
+    q.pixel_shuffle = (pixel_shuffle || kind == 2) ? 1 : 0;
+    if (q.pixel_shuffle) { q.outH *= 2; q.outW *= 2; }
+    return PC_OK;
+}
+
 // generic conv over NHWC segments -> NHWC output slice (channel offset folded into `out`, pixel stride ldo)
 struct Group1 { const ConvW* w; const float* seg0; float* out; };   // second GEMM of a grouped launch
 
@@ -466,22 +502,11 @@ int conv_n(hipStream_t st, const ConvW& w, const Seg* segs, int nseg, int B, int
         q.seg[q.nseg].ptr = s.p; q.seg[q.nseg].ld = s.ld; q.seg[q.nseg].nch = s.nch; ++q.nseg; cin += s.nch;
     }
     if (cin != w.Cin) return PC_ERR_ARG;
-    q.Cin = cin; q.B = B; q.H = H; q.W = W;
+    q.Cin = cin;
     q.w = w.w; q.wlayout = w.layout; q.bias = w.b; q.Cout = w.Cout;
     q.epi = epi; q.aux0 = aux0; q.ld0 = ld0; q.aux1 = aux1; q.ld1 = ld1;
     q.out = out; q.out_relu = out_relu;
-    if (w.kind == 0) {
-        fill_conv_taps(q, w.k, stride);
-        q.Ho = (H + 2 * (w.k / 2) - w.k) / stride + 1;
-        q.Wo = (W + 2 * (w.k / 2) - w.k) / stride + 1;
-        q.outH = q.Ho; q.outW = q.Wo;
-    } else {
-        fill_deconv_taps(q);
-        q.Ho = H; q.Wo = W; q.outH = 2 * H; q.outW = 2 * W;
-    }
-    q.M = B * q.Ho * q.Wo;
-    q.pixel_shuffle = pixel_shuffle ? 1 : 0;
-    if (pixel_shuffle) { q.outH *= 2; q.outW *= 2; }
+    PCCHK(conv_geometry(q, w.kind == 0 ? 0 : 1, w.k, stride, H, W, B, pixel_shuffle));
     q.out_sc = 1; q.out_sx = ldo; q.out_sy = (int64_t)q.outW * ldo; q.out_sb = (int64_t)q.outH * q.outW * ldo;
     if (g1) {
         if (g1->w->Cin != w.Cin || g1->w->Cout != w.Cout || g1->w->k != w.k || g1->w->layout != 1 || w.layout != 1) return PC_ERR_ARG;
@@ -681,13 +706,9 @@ int g_s(pc_codec* c, hipStream_t st, const GsW& g, const float* yhat, int B, int
     {   // deconv 192 -> 3 in sub-pixel form (load_deconv3_subpixel), output written NCHW with clamp
         pc_conv_params q;
         std::memset(&q, 0, sizeof(q));
-        const int H = 8 * h, W = 8 * w;
         q.nseg = 1; q.seg[0].ptr = t1; q.seg[0].ld = NCH; q.seg[0].nch = NCH; q.Cin = NCH;
-        q.B = B; q.H = H; q.W = W;
-        fill_subpixel_taps(q);
+        PCCHK(conv_geometry(q, 2, 3, 1, 8 * h, 8 * w, B, true));
         q.w = g.d8.w; q.wlayout = 1; q.bias = g.d8.b; q.Cout = 12;
-        q.Ho = H; q.Wo = W; q.outH = 2 * H; q.outW = 2 * W; q.M = B * H * W;
-        q.pixel_shuffle = 1;
         q.out = x_hat; q.out_sx = 1; q.out_sy = q.outW; q.out_sc = (int64_t)q.outH * q.outW; q.out_sb = 3 * q.out_sc;
         q.epi = epi;
         PCCHK(launch_conv(q, st));
@@ -912,19 +933,11 @@ extern "C" int pc_conv2d_nhwc(const float* x, int B, int H, int W, int Cin, cons
     pc_conv_params q;
     std::memset(&q, 0, sizeof(q));
     q.nseg = 1; q.seg[0].ptr = x; q.seg[0].ld = Cin; q.seg[0].nch = Cin; q.Cin = Cin;
-    q.B = B; q.H = H; q.W = W;
     if (Cin % 16) { q.smallc = 1; q.in_sc = 1; q.in_sx = Cin; q.in_sy = (int64_t)W * Cin; q.in_sb = (int64_t)H * W * Cin; if (kind != 0) return PC_ERR_ARG; }
     q.w = w_packed; q.bias = bias; q.Cout = Cout; q.epi = act ? PC_EPI_GELU : PC_EPI_NONE; q.tile_cfg = tile_cfg;
     q.wlayout = pc_conv_weight_layout(kind, Cin, Cout, k);
-    if (kind == 0) {
-        fill_conv_taps(q, k, stride);
-        q.Ho = (H + 2 * (k / 2) - k) / stride + 1; q.Wo = (W + 2 * (k / 2) - k) / stride + 1; q.outH = q.Ho; q.outW = q.Wo;
-    } else {
-        if (k != 5) return PC_ERR_ARG;
-        fill_deconv_taps(q);
-        q.Ho = H; q.Wo = W; q.outH = 2 * H; q.outW = 2 * W;
-    }
-    q.M = B * q.Ho * q.Wo;
+    if (kind != 0 && k != 5) return PC_ERR_ARG;
+    PCCHK(conv_geometry(q, kind == 0 ? 0 : 1, k, stride, H, W, B, false));
     q.out = out; q.out_sc = 1; q.out_sx = Cout; q.out_sy = (int64_t)q.outW * Cout; q.out_sb = (int64_t)q.outH * q.outW * Cout;
     return pc_conv_launch(q, (hipStream_t)stream);
 }
@@ -940,30 +953,15 @@ extern "C" int pc_test_conv(const pc_test_conv_desc* d, int* plan, void* stream)
     for (int s = 0; s < d->nseg; ++s) { q.seg[s].ptr = d->seg_ptr[s]; q.seg[s].ld = d->seg_ld[s]; q.seg[s].nch = d->seg_nch[s]; }
     q.smallc = d->smallc ? 1 : 0;
     q.in_sb = d->in_sb; q.in_sy = d->in_sy; q.in_sx = d->in_sx; q.in_sc = d->in_sc;
-    q.Cin = d->Cin; q.B = d->B; q.H = d->H; q.W = d->W;
+    q.Cin = d->Cin;
     q.square = d->square ? 1 : 0;
     q.w = d->w; q.bias = d->bias; q.Cout = d->Cout; q.tile_cfg = d->tile_cfg;
     q.epi = d->epi; q.aux0 = d->aux0; q.ld0 = d->ld0; q.aux1 = d->aux1; q.ld1 = d->ld1;
     q.fg_gamma = d->fg_gamma; q.fg_beta = d->fg_beta;
-    if (d->kind == 0) {
-        if (d->k <= 0 || d->k > 5 || d->stride <= 0) return PC_ERR_ARG;
-        fill_conv_taps(q, d->k, d->stride);
-        q.Ho = (d->H + 2 * (d->k / 2) - d->k) / d->stride + 1; q.Wo = (d->W + 2 * (d->k / 2) - d->k) / d->stride + 1;
-        q.outH = q.Ho; q.outW = q.Wo;
-        q.wlayout = q.square ? 1 : pc_conv_weight_layout(0, d->Cin, d->Cout, d->k);
-    } else if (d->kind == 1) {
-        fill_deconv_taps(q);
-        q.Ho = d->H; q.Wo = d->W; q.outH = 2 * d->H; q.outW = 2 * d->W;
-        q.wlayout = pc_conv_weight_layout(1, d->Cin, d->Cout, 5);
-    } else if (d->kind == 2) {
-        if (d->Cout != 12) return PC_ERR_ARG;
-        fill_subpixel_taps(q);
-        q.Ho = d->H; q.Wo = d->W; q.outH = d->H; q.outW = d->W;
-        q.wlayout = 1;
-    } else return PC_ERR_ARG;
-    q.M = d->B * q.Ho * q.Wo;
-    q.pixel_shuffle = (d->pixel_shuffle || d->kind == 2) ? 1 : 0;
-    if (q.pixel_shuffle) { q.outH *= 2; q.outW *= 2; }
+    if (d->kind == 2 && d->Cout != 12) return PC_ERR_ARG;
+    PCCHK(conv_geometry(q, d->kind, d->k, d->stride, d->H, d->W, d->B, d->pixel_shuffle != 0));
+    if (d->kind == 0) q.wlayout = q.square ? 1 : pc_conv_weight_layout(0, d->Cin, d->Cout, d->k);
+    else q.wlayout = d->kind == 1 ? pc_conv_weight_layout(1, d->Cin, d->Cout, 5) : 1;
     q.out = d->out; q.out_sb = d->out_sb; q.out_sy = d->out_sy; q.out_sx = d->out_sx; q.out_sc = d->out_sc;
     q.out_relu = d->out_relu;
     if (d->ngroup == 2) { q.ngroup = 2; q.g1_seg0 = d->g1_seg0; q.g1_w = d->g1_w; q.g1_bias = d->g1_bias; q.g1_out = d->g1_out; }
@@ -1059,11 +1057,10 @@ extern "C" int pc_mask_quantile_threshold(const float* scale, int ld, int B, int
     return pc_quantile_thr_launch(scale, ld, B, HW, C, q, thr, nullptr, (hipStream_t)stream);
 }
 
-namespace {
-int prep_encode(const float* scale, int ld_scale, const float* mu, int ld_mu, const float* y, int ld_y, const float* ybase, int ld_ybase,
-                const float* thr, int mask_mode, int B, int HW, const float* scale_table, int n_table, float scale_bound, int32_t* sym,
-                int32_t* idx, float* mask, float* yhat, int ld_yhat, float* lik, int64_t lik_sb, hipStream_t stream,
-                const float* mask_src = nullptr, int64_t mask_sb = 0, const float* yadd = nullptr, int ld_yadd = 0)
+extern "C" int pc_gc_prep_encode(const float* scale, int ld_scale, const float* mu, int ld_mu, const float* y, int ld_y,
+                                 const float* ybase, int ld_ybase, const float* thr, int mask_mode, int B, int HW,
+                                 const float* scale_table, int n_table, float scale_bound,
+                                 int32_t* sym, int32_t* idx, float* mask, float* yhat, int ld_yhat, void* stream)
 {
     if (!scale || !mu || !y || !sym || !idx || !yhat || !scale_table || (mask_mode == 1 && !thr)) return PC_ERR_ARG;
     pc_prep_params p;
@@ -1073,41 +1070,19 @@ int prep_encode(const float* scale, int ld_scale, const float* mu, int ld_mu, co
     p.ybase = ybase; p.ld_ybase = ld_ybase; p.thr = thr; p.mask_mode = mask_mode;
     p.table = scale_table; p.ntable = n_table; p.bound = scale_bound;
     p.sym = sym; p.idx = idx; p.mask = mask; p.yhat = yhat; p.ld_yhat = ld_yhat;
-    p.lik = lik; p.lik_sb = lik_sb; p.mask_src = mask_src; p.mask_sb = mask_sb;
-    p.yadd = yadd; p.ld_yadd = ld_yadd;
-    return pc_prep_enc_launch(p, stream);
-}
-}  // namespace
-
-extern "C" int pc_gc_prep_encode(const float* scale, int ld_scale, const float* mu, int ld_mu, const float* y, int ld_y,
-                                 const float* ybase, int ld_ybase, const float* thr, int mask_mode, int B, int HW,
-                                 const float* scale_table, int n_table, float scale_bound,
-                                 int32_t* sym, int32_t* idx, float* mask, float* yhat, int ld_yhat, void* stream)
-{
-    return prep_encode(scale, ld_scale, mu, ld_mu, y, ld_y, ybase, ld_ybase, thr, mask_mode, B, HW, scale_table, n_table, scale_bound, sym,
-                       idx, mask, yhat, ld_yhat, nullptr, 0, (hipStream_t)stream);
+    return pc_prep_enc_launch(p, (hipStream_t)stream);
 }
 
-namespace {
-int prep_decode_index(const float* scale, int ld_scale, const float* thr, int mask_mode, int B, int HW, const float* scale_table,
-                      int n_table, float scale_bound, int32_t* idx, float* mask, hipStream_t stream, const float* mask_src = nullptr,
-                      int64_t mask_sb = 0, uint8_t* idx8 = nullptr)
+extern "C" int pc_gc_prep_decode_index(const float* scale, int ld_scale, const float* thr, int mask_mode, int B, int HW,
+                                       const float* scale_table, int n_table, float scale_bound, int32_t* idx, float* mask,
+                                       void* stream)
 {
     if (!scale || !idx || !scale_table || (mask_mode == 1 && !thr)) return PC_ERR_ARG;
     pc_prep_params p;
     std::memset(&p, 0, sizeof(p));
     p.B = B; p.HW = HW; p.C = 32; p.scale = scale; p.ld_scale = ld_scale; p.thr = thr; p.mask_mode = mask_mode;
     p.table = scale_table; p.ntable = n_table; p.bound = scale_bound; p.idx = idx; p.mask = mask;
-    p.mask_src = mask_src; p.mask_sb = mask_sb; p.idx8 = idx8;
-    return pc_prep_dec_index_launch(p, stream);
-}
-}  // namespace
-
-extern "C" int pc_gc_prep_decode_index(const float* scale, int ld_scale, const float* thr, int mask_mode, int B, int HW,
-                                       const float* scale_table, int n_table, float scale_bound, int32_t* idx, float* mask,
-                                       void* stream)
-{
-    return prep_decode_index(scale, ld_scale, thr, mask_mode, B, HW, scale_table, n_table, scale_bound, idx, mask, (hipStream_t)stream);
+    return pc_prep_dec_index_launch(p, (hipStream_t)stream);
 }
 
 extern "C" int pc_gc_dequantize(const int32_t* sym, const float* mu, int ld_mu, int B, int HW, float* yhat, int ld_yhat, void* stream)
@@ -1209,39 +1184,62 @@ extern "C" int pc_codec_set_option(pc_codec* c, const char* name, int value)
 
 namespace {
 
+// one analysis transform under key prefix p, Cy output channels (models/cnn.py:34-44, CHProg_cnn.py:131-144)
+int load_ga(pc_codec* c, const std::string& p, int Cy, pc_codec::GaW* g)
+{
+    PCCHK(load_conv(c, p + ".0", 3, NCH, 5, 0, &g->c0));
+    PCCHK(load_gdn(c, p + ".1", NCH, &g->g1));
+    PCCHK(load_conv(c, p + ".2", NCH, NCH, 5, 0, &g->c2));
+    PCCHK(load_gdn(c, p + ".3", NCH, &g->g3));
+    PCCHK(load_wam(c, p + ".4", NCH, 8, 4, &g->w4));
+    PCCHK(load_conv(c, p + ".5", NCH, NCH, 5, 0, &g->c5));
+    PCCHK(load_gdn(c, p + ".6", NCH, &g->g6));
+    PCCHK(load_conv(c, p + ".7", NCH, Cy, 5, 0, &g->c7));
+    return load_wam(c, p + ".8", Cy, 4, 2, &g->w8);
+}
+
+// one synthesis transform under key prefix p (models/cnn.py:45-56, CHProg_cnn.py:149-161)
+int load_gs(pc_codec* c, const std::string& p, GsW* g)
+{
+    PCCHK(load_wam(c, p + ".0", D0, 4, 2, &g->w0));
+    PCCHK(load_conv(c, p + ".1", D0, NCH, 5, 1, &g->d1));
+    PCCHK(load_gdn(c, p + ".2", NCH, &g->g2));
+    PCCHK(load_conv(c, p + ".3", NCH, NCH, 5, 1, &g->d3));
+    PCCHK(load_gdn(c, p + ".4", NCH, &g->g4));
+    PCCHK(load_wam(c, p + ".5", NCH, 8, 4, &g->w5));
+    PCCHK(load_conv(c, p + ".6", NCH, NCH, 5, 1, &g->d6));
+    PCCHK(load_gdn(c, p + ".7", NCH, &g->g7));
+    return load_deconv3_subpixel(c, p + ".8", NCH, &g->d8);
+}
+
+// h_a from Cin latent channels: 640, or WACNN's 320 (cnn.py:58)
+int load_ha(pc_codec* c, int Cin)
+{
+    const int ha_c[6] = {Cin, 320, 288, 256, 224, NCH};
+    for (int j = 0; j < 5; ++j) PCCHK(load_conv(c, "h_a." + std::to_string(2 * j), ha_c[j], ha_c[j + 1], 3, 0, &c->ha[j]));
+    return PC_OK;
+}
+
+// the ten base slices' mean / scale / LRP stacks (both models carry them under the same keys)
+int load_base_stacks(pc_codec* c)
+{
+    for (int i = 0; i < NS0; ++i) {
+        const std::string s = "." + std::to_string(i);
+        PCCHK(load_stack5(c, "cc_mean_transforms" + s, D0 + 32 * std::min(i, 5), &c->cc_mean[i]));
+        PCCHK(load_stack5(c, "cc_scale_transforms" + s, D0 + 32 * std::min(i, 5), &c->cc_scale[i]));
+        PCCHK(load_stack5(c, "lrp_transforms" + s, D0 + 32 * std::min(i + 1, 6), &c->lrp[i]));
+    }
+    return PC_OK;
+}
+
 // the transforms of ChannelProgresssiveWACNN (CHProg_cnn.py:131-274)
 int load_channel(pc_codec* c)
 {
     c->multi_enc = c->sd.count("g_a.0.0.weight") != 0;                  // ModuleList of two encoders: keys g_a.<k>.<layer>...
-    for (int k = 0; k < (c->multi_enc ? 2 : 1); ++k) {
-        const std::string p = c->multi_enc ? "g_a." + std::to_string(k) : std::string("g_a");
-        const int Cy = c->multi_enc ? D0 : MLAT;
-        pc_codec::GaW& g = c->ga[k];
-        PCCHK(load_conv(c, p + ".0", 3, NCH, 5, 0, &g.c0));
-        PCCHK(load_gdn(c, p + ".1", NCH, &g.g1));
-        PCCHK(load_conv(c, p + ".2", NCH, NCH, 5, 0, &g.c2));
-        PCCHK(load_gdn(c, p + ".3", NCH, &g.g3));
-        PCCHK(load_wam(c, p + ".4", NCH, 8, 4, &g.w4));
-        PCCHK(load_conv(c, p + ".5", NCH, NCH, 5, 0, &g.c5));
-        PCCHK(load_gdn(c, p + ".6", NCH, &g.g6));
-        PCCHK(load_conv(c, p + ".7", NCH, Cy, 5, 0, &g.c7));
-        PCCHK(load_wam(c, p + ".8", Cy, 4, 2, &g.w8));
-    }
-    for (int k = 0; k < 2; ++k) {
-        const std::string p = "g_s." + std::to_string(k);
-        GsW& g = c->gs[k];
-        PCCHK(load_wam(c, p + ".0", D0, 4, 2, &g.w0));
-        PCCHK(load_conv(c, p + ".1", D0, NCH, 5, 1, &g.d1));
-        PCCHK(load_gdn(c, p + ".2", NCH, &g.g2));
-        PCCHK(load_conv(c, p + ".3", NCH, NCH, 5, 1, &g.d3));
-        PCCHK(load_gdn(c, p + ".4", NCH, &g.g4));
-        PCCHK(load_wam(c, p + ".5", NCH, 8, 4, &g.w5));
-        PCCHK(load_conv(c, p + ".6", NCH, NCH, 5, 1, &g.d6));
-        PCCHK(load_gdn(c, p + ".7", NCH, &g.g7));
-        PCCHK(load_deconv3_subpixel(c, p + ".8", NCH, &g.d8));
-    }
-    const int ha_c[6] = {MLAT, 320, 288, 256, 224, NCH};
-    for (int j = 0; j < 5; ++j) PCCHK(load_conv(c, "h_a." + std::to_string(2 * j), ha_c[j], ha_c[j + 1], 3, 0, &c->ha[j]));
+    if (!c->multi_enc) PCCHK(load_ga(c, "g_a", MLAT, &c->ga[0]));
+    else for (int k = 0; k < 2; ++k) PCCHK(load_ga(c, "g_a." + std::to_string(k), D0, &c->ga[k]));
+    for (int k = 0; k < 2; ++k) PCCHK(load_gs(c, "g_s." + std::to_string(k), &c->gs[k]));
+    PCCHK(load_ha(c, MLAT));
     if (c->topo.single_hyperprior) {
         // one WACNN-form pair with 640 outputs, keys without a ModuleList index (cnn.py:69-91, CHProg_cnn.py:705-715): [1] is the whole
         // net; [0] shares its first four layers and keeps the first 320 outputs of the last (each output channel is its own chain, so
@@ -1271,11 +1269,9 @@ int load_channel(pc_codec* c)
         }
     }
     const int S = 5 - c->topo.support_deficit;                          // support_progressive_slices (CHProg_cnn.py:235-274)
+    PCCHK(load_base_stacks(c));
     for (int i = 0; i < NS0; ++i) {
         const std::string s = "." + std::to_string(i);
-        PCCHK(load_stack5(c, "cc_mean_transforms" + s, D0 + 32 * std::min(i, 5), &c->cc_mean[i]));
-        PCCHK(load_stack5(c, "cc_scale_transforms" + s, D0 + 32 * std::min(i, 5), &c->cc_scale[i]));
-        PCCHK(load_stack5(c, "lrp_transforms" + s, D0 + 32 * std::min(i + 1, 6), &c->lrp[i]));
         PCCHK(load_stack5(c, "cc_mean_transforms_prog" + s, D0 + 32 * std::min(i + 1, S + 1), &c->cc_mean_p[i]));
         PCCHK(load_stack5(c, "cc_scale_transforms_prog" + s, D0 + 32 * std::min(i + 1, S + 1), &c->cc_scale_p[i]));
         PCCHK(load_stack5(c, "lrp_transforms_prog" + s, D0 + 32 * std::min(i + 2, S + 2), &c->lrp_p[i]));
@@ -1294,37 +1290,12 @@ int load_channel(pc_codec* c)
 int load_wacnn(pc_codec* c)
 {
     c->multi_enc = false;
-    pc_codec::GaW& g = c->ga[0];
-    PCCHK(load_conv(c, "g_a.0", 3, NCH, 5, 0, &g.c0));
-    PCCHK(load_gdn(c, "g_a.1", NCH, &g.g1));
-    PCCHK(load_conv(c, "g_a.2", NCH, NCH, 5, 0, &g.c2));
-    PCCHK(load_gdn(c, "g_a.3", NCH, &g.g3));
-    PCCHK(load_wam(c, "g_a.4", NCH, 8, 4, &g.w4));
-    PCCHK(load_conv(c, "g_a.5", NCH, NCH, 5, 0, &g.c5));
-    PCCHK(load_gdn(c, "g_a.6", NCH, &g.g6));
-    PCCHK(load_conv(c, "g_a.7", NCH, D0, 5, 0, &g.c7));
-    PCCHK(load_wam(c, "g_a.8", D0, 4, 2, &g.w8));
-    GsW& s = c->gs[0];
-    PCCHK(load_wam(c, "g_s.0", D0, 4, 2, &s.w0));
-    PCCHK(load_conv(c, "g_s.1", D0, NCH, 5, 1, &s.d1));
-    PCCHK(load_gdn(c, "g_s.2", NCH, &s.g2));
-    PCCHK(load_conv(c, "g_s.3", NCH, NCH, 5, 1, &s.d3));
-    PCCHK(load_gdn(c, "g_s.4", NCH, &s.g4));
-    PCCHK(load_wam(c, "g_s.5", NCH, 8, 4, &s.w5));
-    PCCHK(load_conv(c, "g_s.6", NCH, NCH, 5, 1, &s.d6));
-    PCCHK(load_gdn(c, "g_s.7", NCH, &s.g7));
-    PCCHK(load_deconv3_subpixel(c, "g_s.8", NCH, &s.d8));
-    const int ha_c[6] = {D0, 320, 288, 256, 224, NCH};
-    for (int j = 0; j < 5; ++j) PCCHK(load_conv(c, "h_a." + std::to_string(2 * j), ha_c[j], ha_c[j + 1], 3, 0, &c->ha[j]));
+    PCCHK(load_ga(c, "g_a", D0, &c->ga[0]));
+    PCCHK(load_gs(c, "g_s", &c->gs[0]));
+    PCCHK(load_ha(c, D0));
     PCCHK(load_hs(c, "h_mean_s", &c->hms[0]));
     PCCHK(load_hs(c, "h_scale_s", &c->hss[0]));
-    for (int i = 0; i < NS0; ++i) {
-        const std::string s5 = "." + std::to_string(i);
-        PCCHK(load_stack5(c, "cc_mean_transforms" + s5, D0 + 32 * std::min(i, 5), &c->cc_mean[i]));
-        PCCHK(load_stack5(c, "cc_scale_transforms" + s5, D0 + 32 * std::min(i, 5), &c->cc_scale[i]));
-        PCCHK(load_stack5(c, "lrp_transforms" + s5, D0 + 32 * std::min(i + 1, 6), &c->lrp[i]));
-    }
-    return PC_OK;
+    return load_base_stacks(c);
 }
 
 }  // namespace
@@ -1527,6 +1498,8 @@ struct ChainCtx {
     pc_codec* c;
     int B, h, w, HW;
     size_t M;                                   // B * HW
+    int zh, zw, ZHW;                            // hyper-latent geometry (h / 4, w / 4)
+    float *z, *z_hat; int32_t* z_sym;           // h_a's output (encoders only), its dequantised form, its symbols: [B][ZHW][192]
     float *y, *lm, *ls, *yb, *ye, *mu, *scale, *thr, *masks;
     float* mut;                                 // total_mu_rep: per enhancement slice mu + y_hat_base[i] (mu_total, CHProg_cnn.py:801-810), or null
     const float *mu_base, *scale_base;          // set 0's per-slice mu / scale: the base half is written there only (second_level_set
@@ -1548,6 +1521,54 @@ struct ChainCtx {
 };
 
 template <typename T> inline T* img(T* p, int b0, size_t per_image) { return p ? p + (size_t)b0 * per_image : nullptr; }
+
+// offset of chain step `step`, images from b0, in the per-step buffers (mu, scale, sym, idx, idx8, masks, mut): [step][B][HW][32]
+size_t slice_off(const ChainCtx& k, int step, int b0) { return (size_t)step * k.M * SLICE + (size_t)b0 * k.HW * SLICE; }
+
+// slice i, images from b0, of a caller's NCHW [B][320][HW] tensor (the custom map, the REM checkpoint); image stride D0 * HW
+const float* nchw_slice(const float* p, const ChainCtx& k, int i, int b0) { return p ? p + ((size_t)b0 * D0 + (size_t)SLICE * i) * k.HW : nullptr; }
+
+// What the mask / index kernels of both directions take for chain step `step`, images [b0, b0+nb): the predicted scale, the mask of an
+// enhancement slice (its threshold and mode, and the custom map's slice when the call has one), the scale table and the index output.
+// The encoder adds mu / y / sym / y_hat, the decoder the byte copy of the indexes.
+pc_prep_params chain_prep(const ChainCtx& k, int step, int b0, int nb)
+{
+    pc_prep_params p;
+    std::memset(&p, 0, sizeof(p));
+    const size_t so = slice_off(k, step, b0);
+    p.B = nb; p.HW = k.HW; p.C = SLICE;
+    p.scale = k.scale + so; p.ld_scale = SLICE;
+    if (step >= NS0) {
+        const int i = step - NS0;
+        p.thr = k.thr + (size_t)i * k.B + b0; p.mask_mode = k.mode;
+        p.mask_src = nchw_slice(k.cust_map, k, i, b0);
+    }
+    p.mask_sb = (int64_t)D0 * (int64_t)k.HW;
+    p.table = k.c->scale_table; p.ntable = k.c->n_table; p.bound = k.c->scale_bound;
+    p.idx = k.idx + so;
+    return p;
+}
+
+// The frame of a chain step on either side.  Before it: when this chain is pipelined against another, slice i starts only after the
+// other chain's event for slice i -- which the host must not look at before it has been recorded.  After it: record this chain's event
+// for the slice and publish the count to the other chain's host thread.
+int chain_wait(const ChainCtx& k, int step, hipStream_t sA)
+{
+    if (!k.waitv) return PC_OK;
+    const int i = step >= NS0 ? step - NS0 : step;
+    if (k.wait_count && !k.wait_count->wait_for(i)) return PC_ERR_STATE;                 // the other chain failed
+    HIPCHK(hipStreamWaitEvent(sA, k.waitv[i], 0));
+    return PC_OK;
+}
+
+int chain_signal(const ChainCtx& k, int step, hipStream_t sA)
+{
+    if (!k.sig) return PC_OK;
+    const int i = step >= NS0 ? step - NS0 : step;
+    HIPCHK(hipEventRecord(k.sig[i], sA));
+    if (k.sig_count) k.sig_count->publish(i + 1);
+    return PC_OK;
+}
 
 int ensure_lanes(pc_codec* c, int n)
 {
@@ -1587,8 +1608,7 @@ int mask_threshold(const ChainCtx& k, int i, int b0, int nb, const float* sc_i, 
     uint32_t* w;
     PCCHK(quantile_work(k, nb, tag, &w));
     if (!k.cust_map) return pc_quantile_thr_launch(sc_i, SLICE, nb, k.HW, SLICE, k.q, thr, w, st);
-    const float* m = k.cust_map + ((size_t)b0 * D0 + (size_t)SLICE * i) * k.HW;
-    return pc_quantile_thr_launch(m, SLICE, nb, k.HW, SLICE, k.q, thr, w, st, (int64_t)D0 * k.HW);
+    return pc_quantile_thr_launch(nchw_slice(k.cust_map, k, i, b0), SLICE, nb, k.HW, SLICE, k.q, thr, w, st, (int64_t)D0 * k.HW);
 }
 
 // ResidualBlock (models/utils.py:59-87): leaky(conv2(leaky(conv1(x)))) + (skip(x) or x)
@@ -1638,8 +1658,8 @@ int rem_refine(const ChainCtx& k, int i, int b0, int nb, float* mu_i, float* sc_
     if (mode_star == 1) PCCHK(pc_quantile_thr_launch(sc_i, SLICE, nb, k.HW, SLICE, qs, thr2, qw, st));
     if (mode_bar == 1) PCCHK(pc_quantile_thr_launch(sc_i, SLICE, nb, k.HW, SLICE, qb, thr2 + k.B, qw, st));
     const float* yb_i = img(k.yb, b0, pi * D0) + 32 * i;
-    const float* mu_b = k.mu_base + (size_t)i * k.M * SLICE + (size_t)b0 * pi * SLICE;  // base step i: mu / scale kept per slice, in set 0
-    const float* sd_b = k.scale_base + (size_t)i * k.M * SLICE + (size_t)b0 * pi * SLICE;
+    const float* mu_b = k.mu_base + slice_off(k, i, b0);                                // base step i: mu / scale kept per slice, in set 0
+    const float* sd_b = k.scale_base + slice_off(k, i, b0);
     // f_ent_prog = enc_enh_entropy_params(scale), or of cat(mu, scale) in the mu_std form (:789)
     const float* x = sc_i; int ldx = SLICE;
     for (int j = 0; j < L.n_sub; ++j) {
@@ -1654,7 +1674,7 @@ int rem_refine(const ChainCtx& k, int i, int b0, int nb, float* mu_i, float* sc_
     if (k.rem_ckpt) {
         float* ck;
         PCCHK(c->buf("rem_ck" + tag, m * 32, &ck));
-        PCCHK(pc_nchw_slice_to_nhwc_launch(k.rem_ckpt + ((size_t)b0 * D0 + (size_t)SLICE * i) * pi, (int64_t)D0 * (int64_t)pi, nb, (int)pi, SLICE, ck, st));
+        PCCHK(pc_nchw_slice_to_nhwc_launch(nchw_slice(k.rem_ckpt, k, i, b0), (int64_t)D0 * (int64_t)pi, nb, (int)pi, SLICE, ck, st));
         x = ck; ldx = SLICE;
     }
     for (int j = 0; j < L.n_sub; ++j) {
@@ -1694,9 +1714,8 @@ int support_count(const pc_codec* c, int i) { return std::min(5 - c->topo.suppor
 void support_segs(const ChainCtx& k, int i, int b0, bool std, Seg* sg, int* n)
 {
     const pc_topology& T = k.c->topo;
-    const size_t off = (size_t)b0 * k.HW * SLICE;
-    auto mu_tot = [&](int j) { return k.mut ? k.mut + (size_t)j * k.M * SLICE + off : k.mu + (size_t)(NS0 + j) * k.M * SLICE + off; };
-    auto sc = [&](int j) { return k.scale + (size_t)(NS0 + j) * k.M * SLICE + off; };
+    auto mu_tot = [&](int j) { return k.mut ? k.mut + slice_off(k, j, b0) : k.mu + slice_off(k, NS0 + j, b0); };
+    auto sc = [&](int j) { return k.scale + slice_off(k, NS0 + j, b0); };
     const int s = support_count(k.c, i);
     for (int e = i - s; e < i; ++e) {
         const float* p;
@@ -1723,11 +1742,16 @@ int joiner(const ChainCtx& k, int i, int b0, int nb, const float* enhanced, hipS
     return conv(st, c->joiner[i][2], {{jb, 64, 64}}, nb, k.h, k.w, 1, ye, D0, PC_EPI_NONE);
 }
 
-// the joiner's per-chain workspaces, created before any lane thread runs
-int joiner_workspace(pc_codec* c, const std::string& tag, size_t m)
+// the workspaces of the chain tagged `tag` over m pixels -- the mean / scale stacks' and the joiner's -- created before any lane
+// thread runs (no allocation inside lanes / threads)
+int chain_workspace(pc_codec* c, const std::string& tag, size_t m)
 {
-    if (!c->topo.joiner_cond) return PC_OK;
     float* d;
+    for (const char* base : {"s5m", "s5s"}) {
+        PCCHK(c->buf(base + tag + "_t0", m * 224, &d));
+        PCCHK(c->buf(base + tag + "_t1", m * 176, &d));
+    }
+    if (!c->topo.joiner_cond) return PC_OK;
     PCCHK(c->buf("jn_pm" + tag, m * SLICE, &d));
     PCCHK(c->buf("jn_a" + tag, m * 64, &d));
     return c->buf("jn_b" + tag, m * 64, &d);
@@ -1741,8 +1765,8 @@ int chain_params(const ChainCtx& k, int step, int b0, int nb, hipStream_t st, co
     const size_t pi = (size_t)k.HW;             // pixels per image
     float* lm = img(k.lm, b0, pi * MLAT); float* ls = img(k.ls, b0, pi * MLAT);
     float* yb = img(k.yb, b0, pi * D0); float* ye = img(k.ye, b0, pi * D0);
-    float* mu_i = k.mu + (size_t)step * k.M * SLICE + (size_t)b0 * pi * SLICE;
-    float* sc_i = k.scale + (size_t)step * k.M * SLICE + (size_t)b0 * pi * SLICE;
+    float* mu_i = k.mu + slice_off(k, step, b0);
+    float* sc_i = k.scale + slice_off(k, step, b0);
     const std::string tm = "s5m" + tag, ts = "s5s" + tag;
     if (step < NS0) {
         const int i = step, ns = std::min(5, i);
@@ -1774,7 +1798,7 @@ int chain_params(const ChainCtx& k, int step, int b0, int nb, hipStream_t st, co
                                                 // residual epilogue -- the same conv value, one f32 add, as torch.add
         float* t1;
         PCCHK(c->buf(tm + "_t1", (size_t)nb * pi * 176, &t1));
-        PCCHK(conv(st, c->cc_mean_p[i].c[4], {{t1, 64, 64}}, nb, k.h, k.w, 1, k.mut + (size_t)i * k.M * SLICE + (size_t)b0 * pi * SLICE, SLICE,
+        PCCHK(conv(st, c->cc_mean_p[i].c[4], {{t1, 64, 64}}, nb, k.h, k.w, 1, k.mut + slice_off(k, i, b0), SLICE,
                    PC_EPI_RES, yb + 32 * i, D0));
     }
     PCCHK(rem_refine(k, i, b0, nb, mu_i, sc_i, st, tag));                               // REM: refined scale before the mask (CHProgREM.py:812-826)
@@ -1826,46 +1850,36 @@ int encode_lane(const ChainCtx& k, int b0, int nb, hipStream_t sA, const std::st
     pc_codec* c = k.c;
     const size_t pi = (size_t)k.HW;
     for (int step = k.step0; step < k.step1; ++step) {
-        if (k.waitv) {                                                                   // pipelined against the other chain
-            const int i = step >= NS0 ? step - NS0 : step;
-            if (k.wait_count && !k.wait_count->wait_for(i)) return PC_ERR_STATE;             // the other chain failed
-            HIPCHK(hipStreamWaitEvent(sA, k.waitv[i], 0));
-        }
+        PCCHK(chain_wait(k, step, sA));
         PCCHK(chain_params(k, step, b0, nb, sA, tag));
-        const size_t so = (size_t)step * k.M * SLICE + (size_t)b0 * pi * SLICE;
+        const size_t so = slice_off(k, step, b0);
+        pc_prep_params p = chain_prep(k, step, b0, nb);
+        p.mu = k.mu + so; p.ld_mu = SLICE; p.y = img(k.y, b0, pi * MLAT) + 32 * step; p.ld_y = MLAT;
+        p.sym = k.sym + so;
         // forward path: likelihood of slice `step` of image b at lik[((b * lik_nch) + 32 * step + c) * HW + p]
-        float* lik = k.lik ? k.lik + ((size_t)b0 * k.lik_nch + (size_t)32 * step) * pi : nullptr;
-        const int64_t lik_sb = (int64_t)k.lik_nch * (int64_t)pi;
+        p.lik = k.lik ? k.lik + ((size_t)b0 * k.lik_nch + (size_t)32 * step) * pi : nullptr;
+        p.lik_sb = (int64_t)k.lik_nch * (int64_t)pi;
         if (step < NS0) {                                                                // base slices, :729-764
-            PCCHK(prep_encode(k.scale + so, SLICE, k.mu + so, SLICE, img(k.y, b0, pi * MLAT) + 32 * step, MLAT, nullptr, 0, nullptr, 0,
-                              nb, k.HW, c->scale_table, c->n_table, c->scale_bound, k.sym + so, k.idx + so, nullptr,
-                              img(k.yb, b0, pi * D0) + 32 * step, D0, lik, lik_sb, sA));
+            p.yhat = img(k.yb, b0, pi * D0) + 32 * step; p.ld_yhat = D0;
+            PCCHK(pc_prep_enc_launch(p, sA));
         } else {                                                                         // enhancement slices, :775-845
             const int i = step - NS0;
             const pc_topology& T = c->topo;
-            float* m = k.masks ? k.masks + (size_t)i * k.M * SLICE + (size_t)b0 * pi * SLICE : nullptr;
+            p.mask = k.masks ? k.masks + slice_off(k, i, b0) : nullptr;
             // forward with residual_before_lrp (:1153-1154): "res" adds the base slice in the prep kernel, "cond" runs the joiner on the
             // dequantised slice first; the LRP then refines the merged slice in place
             const bool rbl = T.residual_before_lrp && k.lik;
-            float* yh = img(k.ye, b0, pi * D0) + 32 * i;
-            int ld_yh = D0;
-            if (rbl && T.joiner_cond) { PCCHK(c->buf("jn_pm" + tag, (size_t)nb * pi * SLICE, &yh)); ld_yh = SLICE; }
-            const float* yadd = (rbl && !T.joiner_cond) ? img(k.yb, b0, pi * D0) + 32 * i : nullptr;
-            PCCHK(prep_encode(k.scale + so, SLICE, k.mu + so, SLICE, img(k.y, b0, pi * MLAT) + 32 * step, MLAT,
-                              T.no_delta_encode ? nullptr : img(k.y, b0, pi * MLAT) + 32 * i, MLAT,       // delta_encode :780-781
-                              k.thr + (size_t)i * k.B + b0, k.mode, nb, k.HW,
-                              c->scale_table, c->n_table, c->scale_bound, k.sym + so, k.idx + so, m,
-                              yh, ld_yh, lik, lik_sb, sA,
-                              k.cust_map ? k.cust_map + ((size_t)b0 * D0 + (size_t)SLICE * i) * pi : nullptr, (int64_t)D0 * (int64_t)pi,
-                              yadd, D0));
-            if (rbl && T.joiner_cond) PCCHK(joiner(k, i, b0, nb, yh, sA, tag));
+            p.yhat = img(k.ye, b0, pi * D0) + 32 * i; p.ld_yhat = D0;
+            if (rbl && T.joiner_cond) { PCCHK(c->buf("jn_pm" + tag, (size_t)nb * pi * SLICE, &p.yhat)); p.ld_yhat = SLICE; }
+            if (rbl && !T.joiner_cond) p.yadd = img(k.yb, b0, pi * D0) + 32 * i;
+            p.ld_yadd = D0;
+            if (!T.no_delta_encode) p.ybase = img(k.y, b0, pi * MLAT) + 32 * i;          // delta_encode :780-781
+            p.ld_ybase = MLAT;
+            PCCHK(pc_prep_enc_launch(p, sA));
+            if (rbl && T.joiner_cond) PCCHK(joiner(k, i, b0, nb, p.yhat, sA, tag));
         }
         PCCHK(chain_lrp(k, step, b0, nb, sA, tag));
-        if (k.sig) {
-            const int i = step >= NS0 ? step - NS0 : step;
-            HIPCHK(hipEventRecord(k.sig[i], sA));
-            if (k.sig_count) k.sig_count->publish(i + 1);
-        }
+        PCCHK(chain_signal(k, step, sA));
     }
     return PC_OK;
 }
@@ -1875,43 +1889,33 @@ int decode_lane(const ChainCtx& k, int b0, int nb, hipStream_t sA, const std::st
 {
     pc_codec* c = k.c;
     HIPCHK(hipSetDevice(c->device));
-    g_rowtabs = c->rowtabs;                                                             // (this may be a lane's own host thread)
-    g_prof = c->profile ? c : nullptr;
+    LaunchState launch(c);                                                              // (this may be a lane's own host thread)
     const size_t pi = (size_t)k.HW, per = (size_t)SLICE * k.HW;
     int32_t* h_idx = c->h_idx + k.h_off + (size_t)b0 * per;
     int32_t* h_sym = c->h_sym + k.h_off + (size_t)b0 * per;
     for (int step = k.step0; step < k.step1; ++step) {
-        if (k.waitv) {                                                                   // pipelined against the other chain
-            const int i = step >= NS0 ? step - NS0 : step;
-            if (k.wait_count && !k.wait_count->wait_for(i)) return PC_ERR_STATE;             // the other chain failed
-            HIPCHK(hipStreamWaitEvent(sA, k.waitv[i], 0));
-        }
+        PCCHK(chain_wait(k, step, sA));
         PCCHK(chain_params(k, step, b0, nb, sA, tag));
-        const size_t so = (size_t)step * k.M * SLICE + (size_t)b0 * pi * SLICE;
+        const size_t so = slice_off(k, step, b0);
         const bool e = step >= NS0;
         const int i = e ? step - NS0 : step;
         // the host coder reads the indexes back as bytes (a quarter of the int32 traffic on the per-slice critical path)
-        PCCHK(prep_decode_index(k.scale + so, SLICE, e ? k.thr + (size_t)i * k.B + b0 : nullptr, e ? k.mode : 0, nb, k.HW,
-                                c->scale_table, c->n_table, c->scale_bound, k.idx + so, nullptr, sA,
-                                (e && k.cust_map) ? k.cust_map + ((size_t)b0 * D0 + (size_t)SLICE * i) * pi : nullptr, (int64_t)D0 * (int64_t)pi,
-                                k.idx8 + so));
+        pc_prep_params p = chain_prep(k, step, b0, nb);
+        p.idx8 = k.idx8 + so;
+        PCCHK(pc_prep_dec_index_launch(p, sA));
         uint8_t* h_idx8 = reinterpret_cast<uint8_t*>(h_idx);
         HIPCHK(hipMemcpyAsync(h_idx8, k.idx8 + so, per * nb, hipMemcpyDeviceToHost, sA));
         HIPCHK(hipStreamSynchronize(sA));
-        const auto td0 = std::chrono::steady_clock::now();
+        const double td0 = now_ms();
         const size_t slot = e ? (size_t)NS0 + (size_t)NS0 * k.level + i : (size_t)step;
         PCCHK(pc::rans_decode_u8_batch(y_strings + slot * k.B + b0, y_lens + slot * k.B + b0, nb, h_idx8, per, c->gc.dec(), h_sym, nt));   // :894,969
-        { std::lock_guard<std::mutex> lk(c->buf_mu); c->t_host_decode_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - td0).count(); }
+        { std::lock_guard<std::mutex> lk(c->buf_mu); c->t_host_decode_ms += now_ms() - td0; }
         HIPCHK(hipMemcpyAsync(k.sym + so, h_sym, per * nb * 4, hipMemcpyHostToDevice, sA));
         float* dst = e ? img(k.ye, b0, pi * D0) + 32 * i : img(k.yb, b0, pi * D0) + 32 * i;
         PCCHK(pc_gc_dequantize(k.sym + so, k.mu + so, SLICE, nb, k.HW, dst, D0, sA));                                          // :896,971
         PCCHK(chain_lrp(k, step, b0, nb, sA, tag));
         // the H2D copy out of h_sym is ordered before the next step's host decode by that step's hipStreamSynchronize(sA)
-        if (k.sig) {
-            const int i = step >= NS0 ? step - NS0 : step;
-            HIPCHK(hipEventRecord(k.sig[i], sA));
-            if (k.sig_count) k.sig_count->publish(i + 1);
-        }
+        PCCHK(chain_signal(k, step, sA));
     }
     return PC_OK;
 }
@@ -1925,16 +1929,9 @@ int run_chain(const ChainCtx& k, hipStream_t st, bool decode, const uint8_t* con
                       : encode_lane(k, 0, k.B, st, "");
     const int nl = lane_count(c, k.B, decode);
     PCCHK(ensure_lanes(c, nl));
-    // pre-create every lane's workspace (no allocation inside lanes / threads)
     for (int g = 0; g < nl; ++g) {
         const int b0 = (int)((long)k.B * g / nl), nb = (int)((long)k.B * (g + 1) / nl) - b0;
-        const size_t m = (size_t)nb * k.HW;
-        float* dummy;
-        for (const char* base : {"s5m", "s5s"}) {
-            PCCHK(c->buf(std::string(base) + std::to_string(g) + "_t0", m * 224, &dummy));
-            PCCHK(c->buf(std::string(base) + std::to_string(g) + "_t1", m * 176, &dummy));
-        }
-        PCCHK(joiner_workspace(c, std::to_string(g), m));
+        PCCHK(chain_workspace(c, std::to_string(g), (size_t)nb * k.HW));
     }
     HIPCHK(hipEventRecord(c->eFork, st));
     for (int g = 0; g < nl; ++g) HIPCHK(hipStreamWaitEvent(c->lanes[g].sA, c->eFork, 0));     // every fallible fork step BEFORE a thread exists
@@ -2028,24 +2025,40 @@ int ensure_pipeline(pc_codec* c, size_t M)
         c->pipe_ev.resize(NS0 + 2);
         for (auto& e : c->pipe_ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     }
-    float* dummy;                                     // both chains' stack workspaces, allocated up front
-    for (const char* tag : {"s5mPA", "s5sPA", "s5mPB", "s5sPB"}) {
-        PCCHK(c->buf(std::string(tag) + "_t0", M * 224, &dummy));
-        PCCHK(c->buf(std::string(tag) + "_t1", M * 176, &dummy));
-    }
-    for (const char* tag : {"PA", "PB"}) PCCHK(joiner_workspace(c, tag, M));
+    for (const char* tag : {"PA", "PB"}) PCCHK(chain_workspace(c, tag, M));    // both chains' workspaces, allocated up front
+    return PC_OK;
+}
+
+// pipe_stream beside the caller's stream `st`: fork = pipe_stream goes on from where `st` is now, join = `st` goes on once
+// pipe_stream has run what is queued on it
+int pipe_fork(pc_codec* c, hipStream_t st)
+{
+    HIPCHK(hipEventRecord(c->pipe_ev[NS0], st));
+    HIPCHK(hipStreamWaitEvent(c->pipe_stream, c->pipe_ev[NS0], 0));
+    return PC_OK;
+}
+
+int pipe_join(pc_codec* c, hipStream_t st)
+{
+    HIPCHK(hipEventRecord(c->pipe_ev[NS0 + 1], c->pipe_stream));
+    HIPCHK(hipStreamWaitEvent(st, c->pipe_ev[NS0 + 1], 0));
     return PC_OK;
 }
 
 // The chain's buffers, under the names the taps read (pc_codec_read_tap), and the base pass's context over them: geometry, steps
 // [0, NS0), mu_base / scale_base on set 0.  `y` is the encoders' only, `idx8` the decoder's.  compress and decompress consume the
 // custom map and the REM checkpoint given for the call; forward takes neither and leaves them for the next call.
+// The call's geometry comes from (a, b): the image's (H, W) on the encoder side (multiples of 64), the hyper-latent's (zh, zw) for
+// decompress.  Also the last-call geometry of the taps and the hyper-latent's buffers; `z` is the encoders' only.
 enum class CallKind { compress, forward, decompress };
 
-int chain_setup(pc_codec* c, CallKind kind, int B, int h, int w, ChainCtx* k)
+int call_setup(pc_codec* c, CallKind kind, int B, int a, int b, ChainCtx* k)
 {
     std::memset(k, 0, sizeof(*k));
-    const size_t M = (size_t)B * h * w;
+    const int zh = kind == CallKind::decompress ? a : a / 64, zw = kind == CallKind::decompress ? b : b / 64;
+    const int h = 4 * zh, w = 4 * zw;
+    const size_t M = (size_t)B * h * w, MZ = (size_t)B * zh * zw * NCH;
+    c->last_B = B; c->last_h16 = h; c->last_w16 = w;
     if (kind != CallKind::decompress) PCCHK(c->buf("y", M * MLAT, &k->y));
     PCCHK(c->buf("latent_means", M * MLAT, &k->lm));
     PCCHK(c->buf("latent_scales", M * MLAT, &k->ls));
@@ -2058,7 +2071,11 @@ int chain_setup(pc_codec* c, CallKind kind, int B, int h, int w, ChainCtx* k)
     PCCHK(c->buf("sym", M * SLICE * 2 * NS0, &k->sym));
     PCCHK(c->buf("idx", M * SLICE * 2 * NS0, &k->idx));
     if (kind == CallKind::decompress) PCCHK(c->buf("idx8", M * SLICE * 2 * NS0, &k->idx8));
+    if (kind != CallKind::decompress) PCCHK(c->buf("z", MZ, &k->z));
+    PCCHK(c->buf("z_hat", MZ, &k->z_hat));
+    PCCHK(c->buf("z_sym", MZ, &k->z_sym));
     k->c = c; k->B = B; k->h = h; k->w = w; k->HW = h * w; k->M = M;
+    k->zh = zh; k->zw = zw; k->ZHW = zh * zw;
     k->step0 = 0; k->step1 = NS0;
     k->mu_base = k->mu; k->scale_base = k->scale;
     if (kind != CallKind::forward) {
@@ -2085,8 +2102,7 @@ int encode_pipelined(const ChainCtx& base, const ChainCtx& enh, hipStream_t st, 
 {
     pc_codec* c = base.c;
     PCCHK(ensure_pipeline(c, base.M));
-    HIPCHK(hipEventRecord(c->pipe_ev[NS0], st));
-    HIPCHK(hipStreamWaitEvent(c->pipe_stream, c->pipe_ev[NS0], 0));
+    PCCHK(pipe_fork(c, st));
     ChainCtx kb = base, ke = enh;
     kb.sig = c->pipe_ev.data();
     ke.waitv = c->pipe_ev.data();
@@ -2101,11 +2117,7 @@ int encode_pipelined(const ChainCtx& base, const ChainCtx& enh, hipStream_t st, 
             PCCHK(encode_lane(ke, 0, ke.B, c->pipe_stream, "PB"));                          // :775-845
         }
     }
-    if (join) {
-        HIPCHK(hipEventRecord(c->pipe_ev[NS0 + 1], c->pipe_stream));
-        HIPCHK(hipStreamWaitEvent(st, c->pipe_ev[NS0 + 1], 0));
-    }
-    return PC_OK;
+    return join ? pipe_join(c, st) : PC_OK;
 }
 
 // Two decoder chains side by side: `ka` on `st` from a new host thread, `kb` on pipe_stream from this one, so that each chain's host
@@ -2114,8 +2126,7 @@ int encode_pipelined(const ChainCtx& base, const ChainCtx& enh, hipStream_t st, 
 int decode_pair(const ChainCtx& ka, const ChainCtx& kb, hipStream_t st, const uint8_t* const* y_strings, const size_t* y_lens, int nt)
 {
     pc_codec* c = ka.c;
-    HIPCHK(hipEventRecord(c->pipe_ev[NS0], st));
-    HIPCHK(hipStreamWaitEvent(c->pipe_stream, c->pipe_ev[NS0], 0));
+    PCCHK(pipe_fork(c, st));
     int ra = PC_OK;
     std::thread ta([&] {
         ra = decode_lane(ka, 0, ka.B, st, "PA", y_strings, y_lens, nt);
@@ -2124,13 +2135,11 @@ int decode_pair(const ChainCtx& ka, const ChainCtx& kb, hipStream_t st, const ui
     const int rb = decode_lane(kb, 0, kb.B, c->pipe_stream, "PB", y_strings, y_lens, nt);
     ta.join();
     // join pipe_stream back into `st` whatever happened: a failed call must not leave work of its own running beside the next one
-    const hipError_t ej = hipEventRecord(c->pipe_ev[NS0 + 1], c->pipe_stream);
-    const hipError_t ew = ej == hipSuccess ? hipStreamWaitEvent(st, c->pipe_ev[NS0 + 1], 0) : ej;
+    const int rj = pipe_join(c, st);
     if (ra != PC_OK || rb != PC_OK) { (void)hipStreamSynchronize(c->pipe_stream); (void)hipStreamSynchronize(st); }
     if (ra != PC_OK) return ra;
     if (rb != PC_OK) return rb;
-    HIPCHK(ew);
-    return PC_OK;
+    return rj;
 }
 
 // One call at a time per object: its workspaces, streams and staging buffers are the call's.  A second host thread entering the same
@@ -2147,21 +2156,75 @@ struct BusyGuard {
 struct CallOrder {
     pc_codec* c;
     hipStream_t st;
+    bool on;                                     // false: the call was turned away before it touched the object -- nothing to order
     int rc;
-    CallOrder(pc_codec* cc, hipStream_t s) : c(cc), st(s), rc(PC_OK)
+    CallOrder(pc_codec* cc, hipStream_t s, bool go) : c(cc), st(s), on(go), rc(PC_OK)
     {
+        if (!on) return;
         if (!c->call_done) { if (hipEventCreateWithFlags(&c->call_done, hipEventDisableTiming) != hipSuccess) { c->call_done = nullptr; rc = PC_ERR_HIP; } }
         else if (hipStreamWaitEvent(st, c->call_done, 0) != hipSuccess) rc = PC_ERR_HIP;
     }
     ~CallOrder()
     {
+        if (!on) return;
         // whatever path the call left by: work it queued on the object's second chain stream is joined into the caller's stream first
         // (a failed call must not leave a chain of its own running beside the next call)
-        if (c->pipe_stream && c->pipe_ev.size() > (size_t)NS0 + 1 && hipEventRecord(c->pipe_ev[NS0 + 1], c->pipe_stream) == hipSuccess)
-            (void)hipStreamWaitEvent(st, c->pipe_ev[NS0 + 1], 0);
+        if (c->pipe_stream && c->pipe_ev.size() > (size_t)NS0 + 1) (void)pipe_join(c, st);
         if (c->call_done) (void)hipEventRecord(c->call_done, st);
     }
 };
+// The prologue of every call into a codec object, built once the entry point has checked its own arguments and state.  On entry, in this
+// order: the busy flag, the device, the wait on call_done, the launch state of the caller's thread.  On whatever path the call leaves by,
+// in reverse: the launch state back to what it was, pipe_stream joined, call_done recorded, the busy flag released.  A new entry point
+// that builds this cannot forget one of them.  rc: PC_OK, or what the entry point returns at once.
+struct CallScope {
+    BusyGuard busy;
+    int rc;
+    CallOrder order;
+    LaunchState launch;
+    CallScope(pc_codec* c, hipStream_t st) : busy(c), rc(enter(c, busy.ok)), order(c, st, rc == PC_OK), launch(rc == PC_OK ? c : nullptr) { if (rc == PC_OK) rc = order.rc; }
+    static int enter(pc_codec* c, bool is_free) { if (!is_free) return PC_ERR_STATE; HIPCHK(hipSetDevice(c->device)); return PC_OK; }
+};
+
+// EntropyBottleneck._build_indexes (entropy_models.py:492-502): the channel of each of the n hyper-latent symbols, [B][192][ZHW]
+void eb_indexes(int32_t* idx, size_t n, int ZHW) { for (size_t e = 0; e < n; ++e) idx[e] = (int32_t)((e / ZHW) % NCH); }
+
+// The encoder side in front of the chain: x -> y -> z -> z_sym, z_hat (-> z_lik on the likelihood paths) -> latent_means, latent_scales.
+// enh: the enhancement half of the hyper-synthesis as well.  The reference lines are compress's (CHProg_cnn.py:692-715), then
+// forward_single_quality's (:1013, compute_hyperprior :399-417), then WACNN's compress and forward (models/cnn.py:215-223, :146-159).
+int encoder_front(const ChainCtx& k, hipStream_t st, const float* x, bool enh, float* z_lik)
+{
+    pc_codec* c = k.c;
+    PCCHK(g_a(c, st, x, k.B, 16 * k.h, 16 * k.w, k.y));                                  // :692 / :1013 / cnn.py:215 / cnn.py:146
+    PCCHK(h_a(c, st, k.y, k.B, k.h, k.w, k.z));                                          // :700 / :399 / cnn.py:218 / cnn.py:148
+    // :702-704 / :401-403 / cnn.py:219-220 / cnn.py:154-156 (round about the medians)
+    PCCHK(pc_eb_quant_launch(k.z, k.B, k.ZHW, NCH, c->medians, k.z_sym, k.z_hat, st));
+    if (z_lik) PCCHK(pc_eb_likelihood_launch(k.z_sym, k.B, k.ZHW, NCH, c->medians, c->eb_net, z_lik, st));   // :400 / cnn.py:149
+    return hyper(c, st, k.z_hat, k.B, k.zh, k.zw, enh ? 1.0 : 0.0, k.lm, k.ls);          // :705-715 / :404-417 / cnn.py:222-223 / cnn.py:158-159
+}
+
+// The decoder side in front of the chain: the z strings -> z_sym -> z_hat -> latent_means, latent_scales; the pinned staging is sized
+// for one slice of the batch.  Reference lines: decompress (CHProg_cnn.py:855-867), then WACNN's (models/cnn.py:294-296).
+int decoder_front(const ChainCtx& k, hipStream_t st, const uint8_t* const* z_strings, const size_t* z_lens, bool enh)
+{
+    pc_codec* c = k.c;
+    const size_t per = (size_t)SLICE * k.HW, per_z = (size_t)NCH * k.ZHW;
+    // decompress() returns with work still in flight -- x_hat, and the chains' LAST host-to-device symbol copies, which read the pinned
+    // staging asynchronously.  The host is about to write that staging again (the z symbols below, then every slice's) and may re-allocate it:
+    // wait until the previous call's chains have run (an event behind its last chain, not behind its synthesis transform).  Round 4: found by
+    // the CodecPipeline test under the env matrix -- the next call's z decode overwrote lane 0's pending symbols of the last slice, 1 run in 8.
+    if (c->staging_pending) { HIPCHK(hipEventSynchronize(c->staging_done)); c->staging_pending = false; }
+    if (!c->staging_done) HIPCHK(hipEventCreateWithFlags(&c->staging_done, hipEventDisableTiming));
+    PCCHK(ensure_host_staging(c, std::max(per * k.B, per_z * k.B)));
+    // z: host rANS decode -> device dequantise   (:855 / cnn.py:294)
+    eb_indexes(c->h_idx, per_z * k.B, k.ZHW);
+    PCCHK(pc_rans_decode_batch(z_strings, z_lens, k.B, c->h_idx, per_z, c->eb.cdf.data(), c->eb.n, c->eb.stride, c->eb.len.data(),
+                               c->eb.off.data(), c->h_sym, c->n_threads == 1 ? 1 : 0));
+    HIPCHK(hipMemcpyAsync(k.z_sym, c->h_sym, per_z * k.B * 4, hipMemcpyHostToDevice, st));
+    PCCHK(pc_eb_dequant_launch(k.z_sym, k.B, k.ZHW, NCH, c->medians, k.z_hat, st));
+    HIPCHK(hipStreamSynchronize(st));   // h_sym is reused by the chain
+    return hyper(c, st, k.z_hat, k.B, k.zh, k.zw, enh ? 1.0 : 0.0, k.lm, k.ls);          // :856-867 / cnn.py:295-296
+}
 
 // compress() for a list of mask levels.  Everything that does not depend on the level -- g_a, h_a, the hyper-latent
 // strings, h_s and the ten base slices (CHProg_cnn.py:692-767) -- runs once; the enhancement chain (:775-845) runs once per
@@ -2176,29 +2239,15 @@ int compress_impl(pc_codec* c, const float* x, int B, int H, int W, const double
     if (mask_pol < PC_MASK_POINT_BASED_STD || mask_pol > PC_MASK_THREE_LEVELS_STD) return PC_ERR_ARG;
     if (!c->finalized || !c->gc.ok() || !c->eb.ok() || c->model != PC_MODEL_CHANNEL) return PC_ERR_STATE;
     if (c->eb.n != NCH) return PC_ERR_STATE;
-    BusyGuard busy(c);
-    if (!busy.ok) return PC_ERR_STATE;
-    HIPCHK(hipSetDevice(c->device));
-    CallOrder order(c, st);
-    if (order.rc != PC_OK) return order.rc;
-    g_prof = c->profile ? c : nullptr;
-    g_rowtabs = c->rowtabs;
-    const int h = H / 16, w = W / 16, zh = H / 64, zw = W / 64, HW = h * w, ZHW = zh * zw;
-    const size_t M = (size_t)B * HW;
+    CallScope call(c, st);
+    if (call.rc != PC_OK) return call.rc;
     bool any_enh = false;
     for (int l = 0; l < n_levels; ++l) any_enh = any_enh || !(qualities[l] <= 0);
-    c->last_B = B; c->last_h16 = h; c->last_w16 = w;
 
     ChainCtx k;
-    PCCHK(chain_setup(c, CallKind::compress, B, h, w, &k));
-    float *z, *z_hat;
-    int32_t* z_sym;
-    PCCHK(c->buf("z", (size_t)B * ZHW * NCH, &z));
-    PCCHK(c->buf("z_hat", (size_t)B * ZHW * NCH, &z_hat));
-    PCCHK(c->buf("z_sym", (size_t)B * ZHW * NCH, &z_sym));
-
-    const size_t n_half = (size_t)NS0 * M * SLICE, n_z = (size_t)B * ZHW * NCH;      // symbols of one pass / of z
-    const size_t per = (size_t)SLICE * HW, per_z = (size_t)NCH * ZHW;
+    PCCHK(call_setup(c, CallKind::compress, B, H, W, &k));
+    const size_t n_half = (size_t)NS0 * k.M * SLICE, n_z = (size_t)B * k.ZHW * NCH;  // symbols of one pass / of z
+    const size_t per = (size_t)SLICE * k.HW, per_z = (size_t)NCH * k.ZHW;
     PCCHK(ensure_host_staging(c, 3 * n_half + n_z));                                // [base][enh A][enh B][z]
     while ((int)c->lvl_events.size() < n_levels + 1) {
         hipEvent_t e;
@@ -2210,14 +2259,10 @@ int compress_impl(pc_codec* c, const float* x, int B, int H, int W, const double
     c->y_strings.assign((size_t)c->res_slices * B, {});
     c->z_strings.assign(B, {});
     static const bool timing = std::getenv("PC_TIMING") != nullptr;
-    auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double t0 = now();
+    const double t0 = now_ms();
     double t_host = 0.0, t_enc_last = 0.0;
 
-    PCCHK(g_a(c, st, x, B, H, W, k.y));                                                  // :692
-    PCCHK(h_a(c, st, k.y, B, h, w, z));                                                  // :700
-    PCCHK(pc_eb_quant_launch(z, B, ZHW, NCH, c->medians, z_sym, z_hat, st));             // :702-704
-    PCCHK(hyper(c, st, z_hat, B, zh, zw, any_enh ? 1.0 : 0.0, k.lm, k.ls));              // :705-715
+    PCCHK(encoder_front(k, st, x, any_enh, nullptr));                                    // :692-715
     // Streaming the last coded level's slices out one by one (side stream) while the rest of its chain ran was removed: the per-slice
     // copies and events cost the overlapped bench 3.4 % (46.7 -> 48.2 MP/s) and bought a sequential caller 0.6 ms of host coding per
     // call -- nothing measurable (profiles/r03_t_streamed_encode_ab.log).
@@ -2226,7 +2271,7 @@ int compress_impl(pc_codec* c, const float* x, int B, int H, int W, const double
     auto base_d2h = [&]() -> int {
         HIPCHK(hipMemcpyAsync(c->h_sym, k.sym, n_half * 4, hipMemcpyDeviceToHost, st));
         HIPCHK(hipMemcpyAsync(c->h_idx, k.idx, n_half * 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(c->h_sym + 3 * n_half, z_sym, n_z * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(c->h_sym + 3 * n_half, k.z_sym, n_z * 4, hipMemcpyDeviceToHost, st));
         HIPCHK(hipEventRecord(c->lvl_events[0], st));
         return PC_OK;
     };
@@ -2253,22 +2298,22 @@ int compress_impl(pc_codec* c, const float* x, int B, int H, int W, const double
     int pending = -1, pending_buf = 0, n_coded = 0;
     int rc = PC_OK;
     auto drain = [&](int what, int bufsel) -> int {
-        const double th = now();
+        const double th = now_ms();
         double te = th;
         int r;
         if (what < 0) {
             HIPCHK(hipEventSynchronize(c->lvl_events[0]));
-            te = now();
-            for (size_t e = 0; e < n_z; ++e) c->h_idx[3 * n_half + e] = (int32_t)((e / ZHW) % NCH);   // EntropyBottleneck._build_indexes :492-502
+            te = now_ms();
+            eb_indexes(c->h_idx + 3 * n_half, n_z, k.ZHW);
             r = encode_streams(c, c->h_sym, c->h_idx, 0, NS0, B, per, c->h_sym + 3 * n_half, c->h_idx + 3 * n_half, per_z);
         } else {
             HIPCHK(hipEventSynchronize(c->lvl_events[1 + what]));
-            te = now();
+            te = now_ms();
             const size_t off = (size_t)(1 + bufsel) * n_half;
             r = encode_streams(c, c->h_sym + off, c->h_idx + off, NS0 + NS0 * what, NS0, B, per, nullptr, nullptr, per_z);
         }
-        t_host += now() - th;
-        t_enc_last = now() - te;                             // pure host rANS time of this pass (the last one is not overlapped)
+        t_host += now_ms() - th;
+        t_enc_last = now_ms() - te;                             // pure host rANS time of this pass (the last one is not overlapped)
         return r;
     };
     for (int l = 0; l < n_levels; ++l) {
@@ -2297,15 +2342,12 @@ int compress_impl(pc_codec* c, const float* x, int B, int H, int W, const double
     }
     const int r = drain(pending, pending_buf);
     if (r != PC_OK) rc = r;
-    if (two_levels) {                                                                    // pipe_stream back into the caller's stream
-        HIPCHK(hipEventRecord(c->pipe_ev[NS0 + 1], c->pipe_stream));
-        HIPCHK(hipStreamWaitEvent(st, c->pipe_ev[NS0 + 1], 0));
-    }
+    if (two_levels) PCCHK(pipe_join(c, st));                                             // pipe_stream back into the caller's stream
     HIPCHK(hipStreamSynchronize(st));                                                    // masks_out complete for the caller
-    c->t_compress_ms = now() - t0; c->t_host_encode_ms = t_host; c->t_host_encode_exposed_ms = t_enc_last;
-    c->n_sym_encoded = (double)B * ZHW * NCH + (double)n_half * (1 + n_coded);
+    c->t_compress_ms = now_ms() - t0; c->t_host_encode_ms = t_host; c->t_host_encode_exposed_ms = t_enc_last;
+    c->n_sym_encoded = (double)n_z + (double)n_half * (1 + n_coded);
     if (timing) std::fprintf(stderr, "[pcodec] compress: %d level(s), %d coded; total %.2f ms; host rANS of the last pass (exposed) %.2f ms\n",
-                             n_levels, n_coded, now() - t0, t_enc_last);
+                             n_levels, n_coded, now_ms() - t0, t_enc_last);
     return rc;
 }
 
@@ -2378,14 +2420,9 @@ extern "C" int pc_codec_post_filter(pc_codec* c, int which, const float* x, int 
     if (!c || !x || !out || B <= 0 || H <= 0 || W <= 0 || (H % 4) || (W % 4)) return PC_ERR_ARG;
     if (!c->finalized || !c->post_mode || c->model != PC_MODEL_CHANNEL) return PC_ERR_STATE;
     if (which < 0 || which >= c->post_mode) return PC_ERR_ARG;
-    BusyGuard busy(c);
-    if (!busy.ok) return PC_ERR_STATE;
-    HIPCHK(hipSetDevice(c->device));
     hipStream_t st = (hipStream_t)stream;
-    CallOrder order(c, st);
-    if (order.rc != PC_OK) return order.rc;
-    g_prof = c->profile ? c : nullptr;
-    g_rowtabs = c->rowtabs;
+    CallScope call(c, st);
+    if (call.rc != PC_OK) return call.rc;
     return unet(c, st, c->unet[which], x, B, H, W, out, PC_EPI_NONE);
 }
 
@@ -2395,32 +2432,16 @@ extern "C" int pc_codec_forward(pc_codec* c, const float* x, int B, int H, int W
     if (!c || !x || !x_hat || !y_lik || !z_lik || B <= 0 || H <= 0 || W <= 0 || (H % 64) || (W % 64)) return PC_ERR_ARG;
     if (mask_pol < PC_MASK_POINT_BASED_STD || mask_pol > PC_MASK_THREE_LEVELS_STD) return PC_ERR_ARG;
     if (!c->finalized || !c->eb_net || c->model != PC_MODEL_CHANNEL) return PC_ERR_STATE;
-    BusyGuard busy(c);
-    if (!busy.ok) return PC_ERR_STATE;
-    HIPCHK(hipSetDevice(c->device));
     hipStream_t st = (hipStream_t)stream;
-    CallOrder order(c, st);
-    if (order.rc != PC_OK) return order.rc;
-    g_prof = c->profile ? c : nullptr;
-    g_rowtabs = c->rowtabs;
-    const int h = H / 16, w = W / 16, zh = H / 64, zw = W / 64, ZHW = zh * zw;
+    CallScope call(c, st);
+    if (call.rc != PC_OK) return call.rc;
     const bool enh = quality != 0 || force_enhanced != 0;                                // :1063 "if quality == 0 and force_enhanced is False"
-    c->last_B = B; c->last_h16 = h; c->last_w16 = w;
 
     ChainCtx k;
-    PCCHK(chain_setup(c, CallKind::forward, B, h, w, &k));
-    float *z, *z_hat;
-    int32_t* z_sym;
-    PCCHK(c->buf("z", (size_t)B * ZHW * NCH, &z));
-    PCCHK(c->buf("z_hat", (size_t)B * ZHW * NCH, &z_hat));
-    PCCHK(c->buf("z_sym", (size_t)B * ZHW * NCH, &z_sym));
+    PCCHK(call_setup(c, CallKind::forward, B, H, W, &k));
     k.lik = y_lik; k.lik_nch = enh ? 2 * D0 : D0;
 
-    PCCHK(g_a(c, st, x, B, H, W, k.y));                                                  // :1013
-    PCCHK(h_a(c, st, k.y, B, h, w, z));                                                  // compute_hyperprior :399
-    PCCHK(pc_eb_quant_launch(z, B, ZHW, NCH, c->medians, z_sym, z_hat, st));             // :401-403
-    PCCHK(pc_eb_likelihood_launch(z_sym, B, ZHW, NCH, c->medians, c->eb_net, z_lik, st));   // :400
-    PCCHK(hyper(c, st, z_hat, B, zh, zw, enh ? 1.0 : 0.0, k.lm, k.ls));                  // :404-417
+    PCCHK(encoder_front(k, st, x, enh, z_lik));                                          // :1013, compute_hyperprior :399-417
     ChainCtx ke = level_ctx(k, 0, quality, mask_pol);
     ke.masks = masks_out;
     if (enh && pipeline_enabled(c) && lane_count(c, B, false) == 1) {
@@ -2429,7 +2450,7 @@ extern "C" int pc_codec_forward(pc_codec* c, const float* x, int B, int H, int W
         PCCHK(run_chain(k, st, false, nullptr, nullptr));                                // :1033-1061
         if (enh) PCCHK(run_chain(ke, st, false, nullptr, nullptr));                      // :1089-1160
     }
-    PCCHK(synth(c, st, c->gs[enh ? 1 : 0], enh ? k.ye : k.yb, B, h, w, x_hat));            // :1065 / :1166-1170
+    PCCHK(synth(c, st, c->gs[enh ? 1 : 0], enh ? k.ye : k.yb, B, k.h, k.w, x_hat));        // :1065 / :1166-1170
     return PC_OK;
 }
 
@@ -2446,48 +2467,22 @@ int decompress_impl(pc_codec* c, const uint8_t* const* y_strings, const size_t* 
     if (!c || !y_strings || !y_lens || !z_strings || !z_lens || !x_hat || !qualities || n_levels < 1 || B <= 0 || zh <= 0 || zw <= 0) return PC_ERR_ARG;
     if (mask_pol < PC_MASK_POINT_BASED_STD || mask_pol > PC_MASK_THREE_LEVELS_STD) return PC_ERR_ARG;
     if (!c->finalized || !c->gc.ok() || !c->eb.ok() || c->eb.n != NCH || c->model != PC_MODEL_CHANNEL) return PC_ERR_STATE;
-    BusyGuard busy(c);
-    if (!busy.ok) return PC_ERR_STATE;
-    HIPCHK(hipSetDevice(c->device));
-    CallOrder order(c, st);
-    if (order.rc != PC_OK) return order.rc;
-    g_prof = c->profile ? c : nullptr;
-    g_rowtabs = c->rowtabs;
-    const int h = 4 * zh, w = 4 * zw, HW = h * w, ZHW = zh * zw;
-    const size_t M = (size_t)B * HW;
+    CallScope call(c, st);
+    if (call.rc != PC_OK) return call.rc;
     bool any_enh = false;
     for (int l = 0; l < n_levels; ++l) any_enh = any_enh || qualities[l] != 0;
-    c->last_B = B; c->last_h16 = h; c->last_w16 = w;
 
     ChainCtx k;
-    PCCHK(chain_setup(c, CallKind::decompress, B, h, w, &k));
-    float* z_hat;
-    int32_t* z_sym;
-    PCCHK(c->buf("z_hat", (size_t)B * ZHW * NCH, &z_hat));
-    PCCHK(c->buf("z_sym", (size_t)B * ZHW * NCH, &z_sym));
-    const size_t per = (size_t)SLICE * HW, per_z = (size_t)NCH * ZHW;
-    // decompress() returns with work still in flight -- x_hat, and the chains' LAST host-to-device symbol copies, which read the pinned
-    // staging asynchronously.  The host is about to write that staging again (the z symbols below, then every slice's) and may re-allocate it:
-    // wait until the previous call's chains have run (an event behind its last chain, not behind its synthesis transform).  Round 4: found by
-    // the CodecPipeline test under the env matrix -- the next call's z decode overwrote lane 0's pending symbols of the last slice, 1 run in 8.
-    if (c->staging_pending) { HIPCHK(hipEventSynchronize(c->staging_done)); c->staging_pending = false; }
-    if (!c->staging_done) HIPCHK(hipEventCreateWithFlags(&c->staging_done, hipEventDisableTiming));
+    PCCHK(call_setup(c, CallKind::decompress, B, zh, zw, &k));
+    const int h = k.h, w = k.w;
+    const size_t M = k.M, per = (size_t)SLICE * k.HW, per_z = (size_t)NCH * k.ZHW;
     struct StagingMark {                         // recorded behind every chain section (`st` has joined the lanes / the second chain stream by then), i.e. in
         pc_codec* c; hipStream_t st; bool marked; // front of the synthesis transforms, whose tail the next call's host work may overlap; and, on whatever
-        void mark() { if (hipEventRecord(c->staging_done, st) == hipSuccess) { c->staging_pending = true; marked = true; } }   // path the call leaves by, at the exit
+        void mark() { if (c->staging_done && hipEventRecord(c->staging_done, st) == hipSuccess) { c->staging_pending = true; marked = true; } }   // path the call leaves by, at the exit
         ~StagingMark() { if (!marked) mark(); }
-    } staging_mark{c, st, false};
-    PCCHK(ensure_host_staging(c, std::max(per * B, per_z * B)));
+    } staging_mark{c, st, false};                // (staging_done exists once decoder_front has waited for the previous call's mark)
+    PCCHK(decoder_front(k, st, z_strings, z_lens, any_enh));                             // :855-867
     const int nt = c->n_threads == 1 ? 1 : 0;
-
-    // z: host rANS decode -> device dequantise   (:855)
-    for (size_t e = 0; e < per_z * B; ++e) c->h_idx[e] = (int32_t)((e / ZHW) % NCH);
-    PCCHK(pc_rans_decode_batch(z_strings, z_lens, B, c->h_idx, per_z, c->eb.cdf.data(), c->eb.n, c->eb.stride, c->eb.len.data(),
-                               c->eb.off.data(), c->h_sym, nt));
-    HIPCHK(hipMemcpyAsync(z_sym, c->h_sym, per_z * B * 4, hipMemcpyHostToDevice, st));
-    PCCHK(pc_eb_dequant_launch(z_sym, B, ZHW, NCH, c->medians, z_hat, st));
-    HIPCHK(hipStreamSynchronize(st));   // h_sym is reused by the lanes
-    PCCHK(hyper(c, st, z_hat, B, zh, zw, any_enh ? 1.0 : 0.0, k.lm, k.ls));              // :856-867
     c->t_host_decode_ms = 0.0;
     int first_enh = -1;
     for (int l = 0; l < n_levels && first_enh < 0; ++l) if (qualities[l] != 0) first_enh = l;
@@ -2608,51 +2603,34 @@ extern "C" int pc_codec_wacnn_compress(pc_codec* c, const float* x, int B, int H
 {
     if (!c || !x || B <= 0 || H <= 0 || W <= 0 || (H % 64) || (W % 64)) return PC_ERR_ARG;
     PCCHK(wacnn_ready(c));
-    BusyGuard busy(c);
-    if (!busy.ok) return PC_ERR_STATE;
-    HIPCHK(hipSetDevice(c->device));
     hipStream_t st = (hipStream_t)stream;
-    CallOrder order(c, st);
-    if (order.rc != PC_OK) return order.rc;
-    g_prof = c->profile ? c : nullptr;
-    g_rowtabs = c->rowtabs;
-    auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double t0 = now();
-    const int h = H / 16, w = W / 16, zh = H / 64, zw = W / 64, ZHW = zh * zw;
-    const size_t M = (size_t)B * h * w;
-    c->last_B = B; c->last_h16 = h; c->last_w16 = w;
+    CallScope call(c, st);
+    if (call.rc != PC_OK) return call.rc;
+    const double t0 = now_ms();
     ChainCtx k;
-    PCCHK(chain_setup(c, CallKind::forward, B, h, w, &k));           // (forward: no custom map / REM checkpoint to consume)
-    float *z, *z_hat;
-    int32_t* z_sym;
-    PCCHK(c->buf("z", (size_t)B * ZHW * NCH, &z));
-    PCCHK(c->buf("z_hat", (size_t)B * ZHW * NCH, &z_hat));
-    PCCHK(c->buf("z_sym", (size_t)B * ZHW * NCH, &z_sym));
-    const size_t n_y = (size_t)NS0 * M * SLICE, n_z = (size_t)B * ZHW * NCH;
+    PCCHK(call_setup(c, CallKind::forward, B, H, W, &k));            // (forward: no custom map / REM checkpoint to consume)
+    const size_t n_y = (size_t)NS0 * k.M * SLICE, n_z = (size_t)B * k.ZHW * NCH;
     PCCHK(ensure_host_staging(c, n_y + n_z));
     c->res_slices = 1; c->res_B = B; c->res_level_coded.clear();
     c->y_strings.assign(1, {});
     c->z_strings.assign(B, {});
 
-    PCCHK(g_a(c, st, x, B, H, W, k.y));                                                  // :215
-    PCCHK(h_a(c, st, k.y, B, h, w, z));                                                  // :218
-    PCCHK(pc_eb_quant_launch(z, B, ZHW, NCH, c->medians, z_sym, z_hat, st));             // :219-220
-    PCCHK(hyper(c, st, z_hat, B, zh, zw, 0.0, k.lm, k.ls));                              // :222-223
+    PCCHK(encoder_front(k, st, x, false, nullptr));                                      // :215-223
     PCCHK(run_chain(k, st, false, nullptr, nullptr));                                    // :237-266
     HIPCHK(hipMemcpyAsync(c->h_sym, k.sym, n_y * 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(c->h_idx, k.idx, n_y * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(c->h_sym + n_y, z_sym, n_z * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(c->h_sym + n_y, k.z_sym, n_z * 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    const double th = now();
-    for (size_t e = 0; e < n_z; ++e) c->h_idx[n_y + e] = (int32_t)((e / ZHW) % NCH);      // EntropyBottleneck._build_indexes
-    PCCHK(encode_streams(c, nullptr, nullptr, 0, 0, B, 0, c->h_sym + n_y, c->h_idx + n_y, (size_t)NCH * ZHW));   // z: one string per image
+    const double th = now_ms();
+    eb_indexes(c->h_idx + n_y, n_z, k.ZHW);
+    PCCHK(encode_streams(c, nullptr, nullptr, 0, 0, B, 0, c->h_sym + n_y, c->h_idx + n_y, (size_t)NCH * k.ZHW));   // z: one string per image
     std::vector<uint8_t>& ys = c->y_strings[0];                                          // y: one stream for the batch (:268-269)
     ys.resize(pc_rans_bound(n_y));
     size_t len = 0;
     PCCHK(pc_rans_encode_with_indexes(c->h_sym, c->h_idx, n_y, c->gc.cdf.data(), c->gc.n, c->gc.stride, c->gc.len.data(), c->gc.off.data(),
                                       ys.data(), ys.size(), &len));
     ys.resize(len);
-    c->t_compress_ms = now() - t0; c->t_host_encode_ms = c->t_host_encode_exposed_ms = now() - th;
+    c->t_compress_ms = now_ms() - t0; c->t_host_encode_ms = c->t_host_encode_exposed_ms = now_ms() - th;
     c->n_sym_encoded = (double)(n_y + n_z);
     return PC_OK;
 }
@@ -2662,35 +2640,14 @@ extern "C" int pc_codec_wacnn_decompress(pc_codec* c, const uint8_t* y, size_t y
 {
     if (!c || !y || !z_strings || !z_lens || !x_hat || B <= 0 || zh <= 0 || zw <= 0) return PC_ERR_ARG;
     PCCHK(wacnn_ready(c));
-    BusyGuard busy(c);
-    if (!busy.ok) return PC_ERR_STATE;
-    HIPCHK(hipSetDevice(c->device));
     hipStream_t st = (hipStream_t)stream;
-    CallOrder order(c, st);
-    if (order.rc != PC_OK) return order.rc;
-    g_prof = c->profile ? c : nullptr;
-    g_rowtabs = c->rowtabs;
-    const int h = 4 * zh, w = 4 * zw, HW = h * w, ZHW = zh * zw;
-    c->last_B = B; c->last_h16 = h; c->last_w16 = w;
+    CallScope call(c, st);
+    if (call.rc != PC_OK) return call.rc;
     ChainCtx k;
-    PCCHK(chain_setup(c, CallKind::decompress, B, h, w, &k));
-    float* z_hat;
-    int32_t* z_sym;
-    PCCHK(c->buf("z_hat", (size_t)B * ZHW * NCH, &z_hat));
-    PCCHK(c->buf("z_sym", (size_t)B * ZHW * NCH, &z_sym));
-    const size_t per = (size_t)SLICE * HW * B, per_z = (size_t)NCH * ZHW;                // symbols of one slice of the batch / of one z
-    // the previous call's last symbol copy may still read the pinned staging (see decompress_impl)
-    if (c->staging_pending) { HIPCHK(hipEventSynchronize(c->staging_done)); c->staging_pending = false; }
-    if (!c->staging_done) HIPCHK(hipEventCreateWithFlags(&c->staging_done, hipEventDisableTiming));
-    PCCHK(ensure_host_staging(c, std::max(per, per_z * B)));
-    const int nt = c->n_threads == 1 ? 1 : 0;
-    for (size_t e = 0; e < per_z * B; ++e) c->h_idx[e] = (int32_t)((e / ZHW) % NCH);
-    PCCHK(pc_rans_decode_batch(z_strings, z_lens, B, c->h_idx, per_z, c->eb.cdf.data(), c->eb.n, c->eb.stride, c->eb.len.data(),
-                               c->eb.off.data(), c->h_sym, nt));                                                             // :294
-    HIPCHK(hipMemcpyAsync(z_sym, c->h_sym, per_z * B * 4, hipMemcpyHostToDevice, st));
-    PCCHK(pc_eb_dequant_launch(z_sym, B, ZHW, NCH, c->medians, z_hat, st));
-    HIPCHK(hipStreamSynchronize(st));                                                    // h_sym is reused below
-    PCCHK(hyper(c, st, z_hat, B, zh, zw, 0.0, k.lm, k.ls));                              // :295-296
+    PCCHK(call_setup(c, CallKind::decompress, B, zh, zw, &k));
+    const int h = k.h, w = k.w, HW = k.HW;
+    const size_t per = (size_t)SLICE * HW * B, per_z = (size_t)NCH * k.ZHW;              // symbols of one slice of the batch / of one z
+    PCCHK(decoder_front(k, st, z_strings, z_lens, false));                               // :294-296
     // the ten slices on the caller's stream, one host decode of the whole batch's slice in between (a single stream: nothing to split
     // over lanes or threads, so lanes_dec / host_threads do not apply)
     uint64_t state[2] = {0, 0};
@@ -2698,15 +2655,16 @@ extern "C" int pc_codec_wacnn_decompress(pc_codec* c, const uint8_t* y, size_t y
     c->t_host_decode_ms = 0.0;
     int rc = PC_OK;
     for (int i = 0; i < NS0 && rc == PC_OK; ++i) {
-        const size_t so = (size_t)i * per;
+        const size_t so = slice_off(k, i, 0);
         PCCHK(chain_params(k, i, 0, B, st, ""));                                         // :306-314
-        PCCHK(prep_decode_index(k.scale + so, SLICE, nullptr, 0, B, HW, c->scale_table, c->n_table, c->scale_bound, k.idx + so, nullptr, st,
-                                nullptr, 0, k.idx8 + so));                                                                    // :316
+        pc_prep_params p = chain_prep(k, i, 0, B);
+        p.idx8 = k.idx8 + so;
+        PCCHK(pc_prep_dec_index_launch(p, st));                                          // :316
         HIPCHK(hipMemcpyAsync(h_idx8, k.idx8 + so, per, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
-        const auto td0 = std::chrono::steady_clock::now();
+        const double td0 = now_ms();
         rc = pc::rans_decode_u8_stream(y, y_len, state, h_idx8, per, c->gc.dec(), c->h_sym);                              // :318
-        c->t_host_decode_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - td0).count();
+        c->t_host_decode_ms += now_ms() - td0;
         if (rc != PC_OK) break;
         HIPCHK(hipMemcpyAsync(k.sym + so, c->h_sym, per * 4, hipMemcpyHostToDevice, st));
         PCCHK(pc_gc_dequantize(k.sym + so, k.mu + so, SLICE, B, HW, k.yb + 32 * i, D0, st));                               // :320
@@ -2725,31 +2683,15 @@ extern "C" int pc_codec_wacnn_forward(pc_codec* c, const float* x, int B, int H,
 {
     if (!c || !x || !x_hat || !y_lik || !z_lik || B <= 0 || H <= 0 || W <= 0 || (H % 64) || (W % 64)) return PC_ERR_ARG;
     if (!c->finalized || !c->eb_net || c->model != PC_MODEL_WACNN) return PC_ERR_STATE;
-    BusyGuard busy(c);
-    if (!busy.ok) return PC_ERR_STATE;
-    HIPCHK(hipSetDevice(c->device));
     hipStream_t st = (hipStream_t)stream;
-    CallOrder order(c, st);
-    if (order.rc != PC_OK) return order.rc;
-    g_prof = c->profile ? c : nullptr;
-    g_rowtabs = c->rowtabs;
-    const int h = H / 16, w = W / 16, zh = H / 64, zw = W / 64, ZHW = zh * zw;
-    c->last_B = B; c->last_h16 = h; c->last_w16 = w;
+    CallScope call(c, st);
+    if (call.rc != PC_OK) return call.rc;
     ChainCtx k;
-    PCCHK(chain_setup(c, CallKind::forward, B, h, w, &k));
-    float *z, *z_hat;
-    int32_t* z_sym;
-    PCCHK(c->buf("z", (size_t)B * ZHW * NCH, &z));
-    PCCHK(c->buf("z_hat", (size_t)B * ZHW * NCH, &z_hat));
-    PCCHK(c->buf("z_sym", (size_t)B * ZHW * NCH, &z_sym));
+    PCCHK(call_setup(c, CallKind::forward, B, H, W, &k));
     k.lik = y_lik; k.lik_nch = D0;
-    PCCHK(g_a(c, st, x, B, H, W, k.y));                                                  // :146
-    PCCHK(h_a(c, st, k.y, B, h, w, z));                                                  // :148
-    PCCHK(pc_eb_quant_launch(z, B, ZHW, NCH, c->medians, z_sym, z_hat, st));             // :154-156 (round about the medians)
-    PCCHK(pc_eb_likelihood_launch(z_sym, B, ZHW, NCH, c->medians, c->eb_net, z_lik, st));   // :149
-    PCCHK(hyper(c, st, z_hat, B, zh, zw, 0.0, k.lm, k.ls));                              // :158-159
+    PCCHK(encoder_front(k, st, x, false, z_lik));                                        // :146-159
     PCCHK(run_chain(k, st, false, nullptr, nullptr));                                    // :165-185
-    return g_s(c, st, c->gs[0], k.yb, B, h, w, x_hat, PC_EPI_NONE);                      // :187, unclamped
+    return g_s(c, st, c->gs[0], k.yb, B, k.h, k.w, x_hat, PC_EPI_NONE);                  // :187, unclamped
 }
 
 extern "C" int pc_codec_read_tap(pc_codec* c, const char* name, float* host_out, size_t cap, size_t* n)
@@ -2841,7 +2783,7 @@ extern "C" int pc_codec_profile_end(pc_codec* c, int64_t* n_launches, double* to
         }
     }
     *n_launches = (int64_t)(c->ev_used / 2); *total_ms = ms; *total_flops = c->prof_flops;
-    c->profile = false; c->ev_used = 0; g_prof = nullptr;
+    c->profile = false; c->ev_used = 0;
     return PC_OK;
 }
 
