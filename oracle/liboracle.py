@@ -32,6 +32,7 @@ _lib = None
 _i32p = np.ctypeslib.ndpointer(np.int32, flags="C_CONTIGUOUS")
 _u32p = np.ctypeslib.ndpointer(np.uint32, flags="C_CONTIGUOUS")
 _f32p = np.ctypeslib.ndpointer(np.float32, flags="C_CONTIGUOUS")
+_f64p = np.ctypeslib.ndpointer(np.float64, flags="C_CONTIGUOUS")
 _u8p = np.ctypeslib.ndpointer(np.uint8, flags="C_CONTIGUOUS")
 
 
@@ -57,6 +58,9 @@ def lib():
                                     _f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
         L.orc_win_attention.argtypes = [_f32p, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                         C.c_float, _f32p]
+        L.orc_msssim.argtypes = [_f32p, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, C.c_float, C.c_float,
+                                 C.c_int, _f32p, C.c_int, C.c_int, _f32p, _f64p, _f32p, _f32p, _f64p, _f64p]
+        L.orc_msssim.restype = C.c_int
         for f in (L.orc_rans_encode, L.orc_rans_decode, L.orc_pmf_to_quantized_cdf):
             f.restype = C.c_int
         _lib = L
@@ -175,3 +179,38 @@ def win_attention(qkv, bias, heads, ws, shift, scale):
     lib().orc_win_attention(qkv.reshape(-1), _c(bias, np.float32).reshape(-1), B, H, W, Cc, heads, ws, shift,
                             np.float32(scale), out.reshape(-1))
     return out
+
+
+def msssim(X, Y, data_range, win_size, win_sigma, K, weights, nonnegative=False, variant=0):
+    """pc_metrics.hip's float32 contract on X, Y [B, C, H, W]; levels = len(weights), or 1 when weights is None.
+    Returns dict(win [ws] f32, slab [per scale: [P, tiles, 2] f64], pooled [per scale >= 1: (X, Y) [P, Hs, Ws] f32],
+    means [levels, 2, B, C] f64, out [B] f64)."""
+    X, Y = _c(X, np.float32), _c(Y, np.float32)
+    B, Cc, H, W = X.shape
+    assert Y.shape == X.shape
+    levels = 1 if weights is None else len(weights)
+    P = B * Cc
+    hw = [(H, W)]
+    for _ in range(1, levels):
+        hw.append(((hw[-1][0] + 1) // 2, (hw[-1][1] + 1) // 2))
+    tiles = [max(0, -(-(h - win_size + 1) // 32)) * max(0, -(-(w - win_size + 1) // 64)) for h, w in hw]
+    win = np.zeros(win_size, np.float32)
+    slab = np.zeros(max(1, 2 * P * sum(tiles)), np.float64)
+    npool = sum(P * h * w for h, w in hw[1:])
+    px, py = np.zeros(max(1, npool), np.float32), np.zeros(max(1, npool), np.float32)
+    means = np.zeros((levels, 2, B, Cc), np.float64)
+    out = np.zeros(B, np.float64)
+    wts = _c(weights if weights is not None else [1.0], np.float32)
+    rc = lib().orc_msssim(X.reshape(-1), Y.reshape(-1), B, Cc, H, W, np.float32(data_range), win_size, np.float32(win_sigma),
+                          np.float32(K[0]), np.float32(K[1]), levels, wts, 1 if nonnegative else 0, variant, win, slab, px, py,
+                          means.reshape(-1), out)
+    if rc:
+        raise ValueError(f"orc_msssim rc={rc}")
+    slabs, pooled, so, po = [], [], 0, 0
+    for s, (h, w) in enumerate(hw):
+        slabs.append(slab[so:so + 2 * P * tiles[s]].reshape(P, tiles[s], 2))
+        so += 2 * P * tiles[s]
+        if s:
+            pooled.append((px[po:po + P * h * w].reshape(P, h, w), py[po:po + P * h * w].reshape(P, h, w)))
+            po += P * h * w
+    return dict(win=win, slab=slabs, pooled=pooled, means=means, out=out)

@@ -421,3 +421,212 @@ ORC_API void orc_win_attention(const float *qkv, const float *bias, int B, int H
         }
     }
 }
+
+/* ------------------------------------------------------------------------- */
+/* MS-SSIM / SSIM, the float32 contract of             */
+/* progressivecodec_amd/metrics_csrc/pc_metrics.hip restated                  */
+/* ------------------------------------------------------------------------- */
+/* Written from the stated order, not from the kernel's indexing:
+ *   window   t_i = expf(-(d*d) / two_s2), d = (float)(i - ws/2), two_s2 = (float)(2 sigma^2 in double); S = (float)(sum of t_i
+ *            accumulated in double, ascending i); g_i = t_i / S.
+ *   H pass   per output row y and input column x, per moment v in (X, Y, X*X, Y*Y, X*Y) (products rounded to float32):
+ *            a = +0; a = fmaf(g_k, v[y+k][x], a) for k = 0 .. ws-1.
+ *   W pass   per output pixel: a = +0; a = fmaf(g_j, h[y][x+j], a) for j = 0 .. ws-1.
+ *   maps     mu1_sq = mu1*mu1, mu2_sq = mu2*mu2, mu12 = mu1*mu2; s1 = m2 - mu1_sq, s2 = m3 - mu2_sq, s12 = m4 - mu12;
+ *            cs = (2*s12 + C2) / ((s1 + s2) + C2); ssim = ((2*mu12 + C1) / ((mu1_sq + mu2_sq) + C1)) * cs; all float32.
+ *   sums     a 32 x 64 output tile is summed in double by 256 "threads": thread t owns row t % 32, columns 8*(t/32) .. +7, added in
+ *            ascending column order onto +0 (pixels outside the plane add nothing); the 64 threads of a wave are folded by
+ *            v[l] += v[l + off], off = 32, 16, .. 1; the four waves are added in order.  Per (scale, plane): lane l of 64 sums tiles
+ *            l, l+64, .. in order, the same fold, then / (Ho * Wo).
+ *   pool     (((a + b) + c) + d) * 0.25f over rows 2oy - (H&1), +1 and columns 2ox - (W&1), +1, zero outside the plane.
+ *   final    levels > 1: per channel prod_s pow(max(m_s, 0), w_s) in double, m_s the CS mean (the SSIM mean at the last scale), product
+ *            in ascending s, channels added in order, / C.  levels == 1: the SSIM mean (relu'd when nonnegative).
+ * variant (tests of the tests only): bit 0 applies the taps in descending order, bit 1 sums the tiles of a plane sequentially. */
+static void msssim_fold(double *v)
+{
+    for (int off = 32; off > 0; off >>= 1)
+        for (int l = 0; l < off; ++l) v[l] += v[l + off];
+}
+
+static void msssim_scale(const float *X, const float *Y, int P, int H, int W, int ws, const float *g, float C1, float C2, int rev,
+                         double *slab)
+{
+    const int Ho = H - ws + 1, Wo = W - ws + 1, ty_n = (Ho + 31) / 32, tx_n = (Wo + 63) / 64, tiles = ty_n * tx_n;
+#pragma omp parallel
+    {
+        float *hv = (float *)malloc(sizeof(float) * 5 * 32 * (size_t)W);
+        float *ssb = (float *)malloc(sizeof(float) * 32 * (size_t)Wo), *csb = (float *)malloc(sizeof(float) * 32 * (size_t)Wo);
+#pragma omp for schedule(dynamic) collapse(2)
+        for (int p = 0; p < P; ++p)
+            for (int ty = 0; ty < ty_n; ++ty) {
+                const float *xp = X + (int64_t)p * H * W, *yp = Y + (int64_t)p * H * W;
+                const int y0 = ty * 32, rows = Ho - y0 < 32 ? Ho - y0 : 32;
+                for (int r = 0; r < rows; ++r) {
+                    float *h0 = hv + (0 * 32 + r) * (size_t)W, *h1 = hv + (1 * 32 + r) * (size_t)W, *h2 = hv + (2 * 32 + r) * (size_t)W;
+                    float *h3 = hv + (3 * 32 + r) * (size_t)W, *h4 = hv + (4 * 32 + r) * (size_t)W;
+                    for (int x = 0; x < W; ++x) h0[x] = h1[x] = h2[x] = h3[x] = h4[x] = 0.0f;
+                    for (int kk = 0; kk < ws; ++kk) {
+                        const int k = rev ? ws - 1 - kk : kk;
+                        const float *xr = xp + (int64_t)(y0 + r + k) * W, *yr = yp + (int64_t)(y0 + r + k) * W;
+                        const float gk = g[k];
+                        for (int x = 0; x < W; ++x) {
+                            const float xv = xr[x], yv = yr[x];
+                            const float xx = xv * xv, yy = yv * yv, xy = xv * yv;
+                            h0[x] = fmaf(gk, xv, h0[x]);
+                            h1[x] = fmaf(gk, yv, h1[x]);
+                            h2[x] = fmaf(gk, xx, h2[x]);
+                            h3[x] = fmaf(gk, yy, h3[x]);
+                            h4[x] = fmaf(gk, xy, h4[x]);
+                        }
+                    }
+                    for (int x = 0; x < Wo; ++x) {
+                        float m[5];
+                        for (int q = 0; q < 5; ++q) {
+                            const float *h = hv + (q * 32 + r) * (size_t)W + x;
+                            float a = 0.0f;
+                            for (int jj = 0; jj < ws; ++jj) {
+                                const int j = rev ? ws - 1 - jj : jj;
+                                a = fmaf(g[j], h[j], a);
+                            }
+                            m[q] = a;
+                        }
+                        const float mu1_sq = m[0] * m[0], mu2_sq = m[1] * m[1], mu12 = m[0] * m[1];
+                        const float s1 = m[2] - mu1_sq, s2 = m[3] - mu2_sq, s12 = m[4] - mu12;
+                        const float cs = (2.0f * s12 + C2) / (s1 + s2 + C2);
+                        csb[r * (size_t)Wo + x] = cs;
+                        ssb[r * (size_t)Wo + x] = ((2.0f * mu12 + C1) / (mu1_sq + mu2_sq + C1)) * cs;
+                    }
+                }
+                for (int tx = 0; tx < tx_n; ++tx) {
+                    double vs[256], vc[256];
+                    for (int t = 0; t < 256; ++t) {
+                        const int r = t % 32, c0 = tx * 64 + (t / 32) * 8;
+                        double a = 0.0, d = 0.0;
+                        if (r < rows)
+                            for (int o = 0; o < 8; ++o)
+                                if (c0 + o < Wo) {
+                                    a += (double)ssb[r * (size_t)Wo + c0 + o];
+                                    d += (double)csb[r * (size_t)Wo + c0 + o];
+                                }
+                        vs[t] = a;
+                        vc[t] = d;
+                    }
+                    double a = 0.0, d = 0.0;
+                    for (int wv = 0; wv < 4; ++wv) {
+                        msssim_fold(vs + 64 * wv);
+                        msssim_fold(vc + 64 * wv);
+                        a = wv ? a + vs[64 * wv] : vs[0];
+                        d = wv ? d + vc[64 * wv] : vc[0];
+                    }
+                    double *o = slab + 2 * ((int64_t)p * tiles + ty * tx_n + tx);
+                    o[0] = a;
+                    o[1] = d;
+                }
+            }
+        free(hv);
+        free(ssb);
+        free(csb);
+    }
+}
+
+static void msssim_pool(const float *X, int P, int H, int W, float *out)
+{
+    const int Hp = (H + 1) / 2, Wp = (W + 1) / 2, ph = H & 1, pw = W & 1;
+#pragma omp parallel for schedule(static) collapse(2)
+    for (int p = 0; p < P; ++p)
+        for (int oy = 0; oy < Hp; ++oy) {
+            const float *xp = X + (int64_t)p * H * W;
+            for (int ox = 0; ox < Wp; ++ox) {
+                float v[4];
+                for (int q = 0; q < 4; ++q) {
+                    const int iy = 2 * oy - ph + q / 2, ix = 2 * ox - pw + q % 2;
+                    v[q] = (iy >= 0 && iy < H && ix >= 0 && ix < W) ? xp[(int64_t)iy * W + ix] : 0.0f;
+                }
+                out[((int64_t)p * Hp + oy) * Wp + ox] = (((v[0] + v[1]) + v[2]) + v[3]) * 0.25f;
+            }
+        }
+}
+
+/* X, Y contiguous [B*C][H][W].  Outputs: win [win_size]; slab [s][plane][tile] (ssim, cs) pairs, tiles of a scale row-major over
+ * ceil(Ho/32) x ceil(Wo/64); poolX / poolY the planes of scales 1 .. levels-1 back to back; means [levels][2][B*C]; out [B] in double
+ * (the library rounds it to float32).  Returns 0, or -1 for arguments outside the library's rules. */
+ORC_API int orc_msssim(const float *X, const float *Y, int B, int C, int H, int W, float data_range, int win_size, float win_sigma,
+                       float K1, float K2, int levels, const float *weights, int nonnegative, int variant, float *win, double *slab,
+                       float *poolX, float *poolY, double *means, double *out)
+{
+    if (B < 1 || C < 1 || win_size < 1 || win_size > 31 || !(win_size & 1) || levels < 1 || levels > 5) return -1;
+    if (levels == 1 ? (H < win_size || W < win_size) : ((H < W ? H : W) <= (win_size - 1) * 16)) return -1;
+    const int P = B * C;
+    float t[31];
+    const float two_s2 = (float)(2.0 * (double)win_sigma * (double)win_sigma);
+    double sum = 0.0;
+    for (int i = 0; i < win_size; ++i) {
+        const float d = (float)(i - win_size / 2);
+        t[i] = expf(-(d * d) / two_s2);
+        sum += (double)t[i];
+    }
+    for (int i = 0; i < win_size; ++i) win[i] = t[i] / (float)sum;
+    const float C1 = (K1 * data_range) * (K1 * data_range), C2 = (K2 * data_range) * (K2 * data_range);
+
+    const float *cx = X, *cy = Y;
+    int h = H, w = W;
+    for (int s = 0; s < levels; ++s) {
+        const int Ho = h - win_size + 1, Wo = w - win_size + 1, tiles = ((Ho + 31) / 32) * ((Wo + 63) / 64);
+        msssim_scale(cx, cy, P, h, w, win_size, win, C1, C2, variant & 1, slab);
+        const double count = (double)Ho * (double)Wo;
+        for (int p = 0; p < P; ++p) {
+            const double *sp = slab + 2 * (int64_t)p * tiles;
+            double vs[64], vc[64];
+            if (variant & 2) {
+                double a = 0.0, d = 0.0;
+                for (int q = 0; q < tiles; ++q) { a += sp[2 * q]; d += sp[2 * q + 1]; }
+                vs[0] = a;
+                vc[0] = d;
+            } else {
+                for (int l = 0; l < 64; ++l) {
+                    double a = 0.0, d = 0.0;
+                    for (int q = l; q < tiles; q += 64) { a += sp[2 * q]; d += sp[2 * q + 1]; }
+                    vs[l] = a;
+                    vc[l] = d;
+                }
+                msssim_fold(vs);
+                msssim_fold(vc);
+            }
+            means[((int64_t)s * 2 + 0) * P + p] = vs[0] / count;
+            means[((int64_t)s * 2 + 1) * P + p] = vc[0] / count;
+        }
+        slab += 2 * (int64_t)P * tiles;
+        if (s + 1 < levels) {
+            msssim_pool(cx, P, h, w, poolX);
+            msssim_pool(cy, P, h, w, poolY);
+            cx = poolX;
+            cy = poolY;
+            h = (h + 1) / 2;
+            w = (w + 1) / 2;
+            poolX += (int64_t)P * h * w;
+            poolY += (int64_t)P * h * w;
+        }
+    }
+    for (int b = 0; b < B; ++b) {
+        double total = 0.0;
+        for (int c = 0; c < C; ++c) {
+            const int p = b * C + c;
+            double v;
+            if (levels == 1) {
+                v = means[p];
+                if (nonnegative && v < 0.0) v = 0.0;
+            } else {
+                v = 1.0;
+                for (int s = 0; s < levels; ++s) {
+                    double m = means[((int64_t)s * 2 + (s == levels - 1 ? 0 : 1)) * P + p];
+                    m = m < 0.0 ? 0.0 : m;
+                    const double term = pow(m, (double)weights[s]);
+                    v = s ? v * term : term;
+                }
+            }
+            total += v;
+        }
+        out[b] = total / C;
+    }
+    return 0;
+}

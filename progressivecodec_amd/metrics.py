@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libpc_metrics.so")
 
 #: every symbol metrics_csrc/pc_metrics.h declares
-EXPORTS = ["pc_msssim_workspace_size", "pc_msssim", "pc_metrics_strerror", "pc_metrics_last_hip_error"]
+EXPORTS = ["pc_msssim_workspace_size", "pc_msssim", "pc_msssim_plan", "pc_metrics_strerror", "pc_metrics_last_hip_error"]
 
 #: the library's default scale weights (Wang, Simoncelli, Bovik 2003)
 MS_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)
@@ -34,6 +34,8 @@ def lib():
         L.pc_msssim_workspace_size.argtypes = [C.c_int] * 6
         L.pc_msssim.argtypes = [vp, i64, i64, i64, vp, i64, i64, i64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float,
                                 C.c_float, C.c_float, C.c_int, C.POINTER(C.c_float), C.c_int, vp, C.c_size_t, vp, vp, vp]
+        L.pc_msssim_plan.argtypes = [vp, i64, i64, i64, vp, i64, i64, i64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp,
+                                     C.POINTER(C.c_int)]
         L.pc_metrics_strerror.restype = C.c_char_p
         L.pc_metrics_strerror.argtypes = [C.c_int]
         _lib = L

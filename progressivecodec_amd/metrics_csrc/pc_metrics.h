@@ -39,6 +39,13 @@ PC_API int pc_msssim(const float* X, int64_t sxb, int64_t sxc, int64_t sxh, cons
                      const float* weights, int nonnegative, void* workspace, size_t workspace_bytes, float* out, double* out_scales,
                      void* stream);
 
+/* Host only, launches nothing: vec[s] for s < levels is 1 where a pc_msssim call with these arguments stages scale s with 16-byte loads
+ * and 0 where it stages it float by float (both give the same bits).  Scale 0 reads X and Y: the 16-byte path needs both bases 16-byte
+ * aligned and all six strides multiples of 4.  Scale s > 0 reads the pooled planes inside `workspace`: it needs a 16-byte aligned
+ * workspace and W_s and H_s*W_s multiples of 4.  pc_msssim decides with the same code.  PC_ERR_ARG as pc_msssim. */
+PC_API int pc_msssim_plan(const float* X, int64_t sxb, int64_t sxc, int64_t sxh, const float* Y, int64_t syb, int64_t syc, int64_t syh,
+                          int B, int C, int H, int W, int win_size, int levels, const void* workspace, int* vec);
+
 PC_API const char* pc_metrics_strerror(int code);
 PC_API int pc_metrics_last_hip_error(void);
 

@@ -311,7 +311,49 @@ const ScaleLaunch kScale[] = {launch_scale<1>, launch_scale<3>, launch_scale<5>,
                               launch_scale<13>, launch_scale<15>, launch_scale<17>, launch_scale<19>, launch_scale<21>,
                               launch_scale<23>, launch_scale<25>, launch_scale<27>, launch_scale<29>, launch_scale<31>};
 
+// The inputs of every scale as the scale and pool kernels read them, and the staging path of each: scale 0 is the caller's X and Y, scale
+// s > 0 the pooled planes in the workspace.  vec = 1 (16-byte staging loads) needs both bases 16-byte aligned and all six strides
+// multiples of four floats.  The one place that decides it: pc_msssim launches from this, pc_msssim_plan reports it.
+struct ScaleView {
+    const float *x, *y;
+    int64_t xb, xc, xh, yb, yc, yh;
+    int vec;
+};
+
+void scale_views(const Geometry& g, int C, const float* X, int64_t sxb, int64_t sxc, int64_t sxh, const float* Y, int64_t syb,
+                 int64_t syc, int64_t syh, const void* workspace, ScaleView* v)
+{
+    const char* ws = static_cast<const char*>(workspace);
+    for (int s = 0; s < g.levels; ++s) {
+        ScaleView& a = v[s];
+        if (s == 0) {
+            a = ScaleView{X, Y, sxb, sxc, sxh, syb, syc, syh, 0};
+        } else {
+            const int64_t hw = (int64_t)g.H[s] * g.W[s];
+            a.x = reinterpret_cast<const float*>(ws + g.pooled_off[s]);
+            a.y = reinterpret_cast<const float*>(ws + g.pooled_off[s] + align256((int64_t)g.P * hw * 4));
+            a.xc = a.yc = hw;
+            a.xb = a.yb = (int64_t)C * hw;
+            a.xh = a.yh = g.W[s];
+        }
+        a.vec = (reinterpret_cast<uintptr_t>(a.x) % 16 == 0 && reinterpret_cast<uintptr_t>(a.y) % 16 == 0 && a.xb % 4 == 0 &&
+                 a.xc % 4 == 0 && a.xh % 4 == 0 && a.yb % 4 == 0 && a.yc % 4 == 0 && a.yh % 4 == 0);
+    }
+}
+
 }  // namespace
+
+extern "C" int pc_msssim_plan(const float* X, int64_t sxb, int64_t sxc, int64_t sxh, const float* Y, int64_t syb, int64_t syc,
+                              int64_t syh, int B, int C, int H, int W, int win_size, int levels, const void* workspace, int* vec)
+{
+    Geometry g;
+    if (!X || !Y || !workspace || !vec || !geometry(B, C, H, W, win_size, levels, g)) return PC_ERR_ARG;
+    if (sxb < 1 || sxc < 1 || sxh < 1 || syb < 1 || syc < 1 || syh < 1) return PC_ERR_ARG;
+    ScaleView v[MAX_LEVELS];
+    scale_views(g, C, X, sxb, sxc, sxh, Y, syb, syc, syh, workspace, v);
+    for (int s = 0; s < levels; ++s) vec[s] = v[s].vec;
+    return PC_OK;
+}
 
 extern "C" size_t pc_msssim_workspace_size(int B, int C, int H, int W, int win_size, int levels)
 {
@@ -359,14 +401,12 @@ extern "C" int pc_msssim(const float* X, int64_t sxb, int64_t sxc, int64_t sxh, 
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     char* ws = static_cast<char*>(workspace);
     double2* slab = reinterpret_cast<double2*>(ws);
-    const float* cx = X;
-    const float* cy = Y;
-    int64_t cxb = sxb, cxc = sxc, cxh = sxh, cyb = syb, cyc = syc, cyh = syh;
+    ScaleView sv[MAX_LEVELS];
+    scale_views(g, C, X, sxb, sxc, sxh, Y, syb, syc, syh, workspace, sv);
     for (int s = 0; s < levels; ++s) {
         const int h = g.H[s], w = g.W[s];
-        const int vec = (reinterpret_cast<uintptr_t>(cx) % 16 == 0 && reinterpret_cast<uintptr_t>(cy) % 16 == 0 && cxb % 4 == 0 &&
-                         cxc % 4 == 0 && cxh % 4 == 0 && cyb % 4 == 0 && cyc % 4 == 0 && cyh % 4 == 0);
-        kScale[win_size / 2](cx, cxb, cxc, cxh, cy, cyb, cyc, cyh, C, h, w, g.tiles_x[s], g.tiles[s], g.P, vec, taps, C1, C2,
+        const ScaleView& a = sv[s];
+        kScale[win_size / 2](a.x, a.xb, a.xc, a.xh, a.y, a.yb, a.yc, a.yh, C, h, w, g.tiles_x[s], g.tiles[s], g.P, a.vec, taps, C1, C2,
                              slab + g.slab_off[s], st);
         HIPCHK(hipGetLastError());
         fa.tiles[s] = g.tiles[s];
@@ -375,17 +415,10 @@ extern "C" int pc_msssim(const float* X, int64_t sxb, int64_t sxc, int64_t sxh, 
         if (s + 1 < levels) {
             const int hp = g.H[s + 1], wp = g.W[s + 1];
             const int64_t n = (int64_t)g.P * hp * wp;
-            float* px = reinterpret_cast<float*>(ws + g.pooled_off[s + 1]);
-            float* py = reinterpret_cast<float*>(ws + g.pooled_off[s + 1] + align256(n * 4));
             const int blocks = (int)(cdiv(n, NT) < 8192 ? cdiv(n, NT) : 8192);
-            hipLaunchKernelGGL(pool2x2_kernel, dim3(blocks), dim3(NT), 0, st, cx, cxb, cxc, cxh, cy, cyb, cyc, cyh, C, h, w, hp, wp, n,
-                               px, py);
+            hipLaunchKernelGGL(pool2x2_kernel, dim3(blocks), dim3(NT), 0, st, a.x, a.xb, a.xc, a.xh, a.y, a.yb, a.yc, a.yh, C, h, w, hp,
+                               wp, n, const_cast<float*>(sv[s + 1].x), const_cast<float*>(sv[s + 1].y));
             HIPCHK(hipGetLastError());
-            cx = px;
-            cy = py;
-            cxc = cyc = (int64_t)hp * wp;
-            cxb = cyb = (int64_t)C * hp * wp;
-            cxh = cyh = wp;
         }
     }
     hipLaunchKernelGGL(msssim_final_kernel, dim3(B), dim3(NT), 0, st, slab, fa, B, out, out_scales);
