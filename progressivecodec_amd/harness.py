@@ -110,8 +110,58 @@ def _write_levels(writing, rows, pr_list, names):
             f.write("SEQUENCE " + "AVG " + "BITS " + str(avg("bpp")) + " YPSNR " + str(avg("psnr")) + " YMSSIM " + str(avg("ms_ssim_db")) + "\n")
 
 
+def _pixel_io_rows(model, img, pr_list, mask_pol, shared_base, ms_ssim):
+    """The rows of one uint8 image [1,3,H,W] (on the device) for compress_with_ac(pixel_io=True): the plain or the shared_base loop with
+    pixels.to_model_input in front and, straight after each level's decode, one pixels.from_model_output(..., ref=img, image=False)
+    behind it: only the level's 48 bytes of sums stay on the device (no 8-bit image is written, no x_hat is kept), and the sums of all
+    levels are read back together at the end."""
+    import torch
+    import torch.nn.functional as F
+    from .pixels import from_model_output, psnr_from_sse, to_model_input
+    h, w = img.shape[2:]
+    x_padded, geom = to_model_input(img, layout="chw")
+    sync = torch.cuda.synchronize
+    sums, msv = [], []
+
+    def measure(out_dec):
+        sums.append(from_model_output(out_dec["x_hat"], geom, ref=img, ref_layout="chw", image=False).sse_f)
+        if ms_ssim:
+            msv.append(_ms_ssim_of(F.pad(x_padded, geom.unpad), F.pad(out_dec["x_hat"], geom.unpad).clamp_(0, 1))[0])
+    if shared_base:
+        datas = model.compress_levels(x_padded, pr_list, mask_pol=mask_pol)
+        sync()
+        t0 = time.time()
+        outs = model.decompress_levels([d["strings"] for d in datas], datas[0]["shape"], pr_list, mask_pol=mask_pol)
+        sync()
+        times = [(time.time() - t0) / len(pr_list)] * len(pr_list)
+        for out_dec in outs:
+            measure(out_dec)
+        strings = [d["strings"] for d in datas]
+        del outs, datas
+    else:
+        strings, times = [], []
+        for p in pr_list:
+            data = model.compress(x_padded, quality=p, mask_pol=mask_pol)
+            strings.append(data["strings"])
+            sync()
+            t0 = time.time()
+            out_dec = model.decompress(data["strings"], data["shape"], quality=p, mask_pol=mask_pol)
+            sync()
+            times.append(time.time() - t0)
+            measure(out_dec)
+            del out_dec, data
+    sse = [r[0][0] + r[0][1] + r[0][2] for r in torch.stack(sums).tolist()] if sums else []    # the one read-back of this image
+    rows = []
+    for k, (p, (y_strings, z_strings), dec_time, e) in enumerate(zip(pr_list, strings, times, sse)):
+        nbytes = sum(len(s[0]) for s in y_strings) + sum(len(s) for s in z_strings)
+        rows.append({"quality": p, "bpp": 8.0 * nbytes / (h * w), "psnr": psnr_from_sse(e, 3 * h * w), "dec_time": dec_time})
+        if ms_ssim:
+            rows[-1].update(ms_ssim=msv[k], ms_ssim_db=_db(msv[k]))
+    return rows
+
+
 def compress_with_ac(model, images, pr_list=None, mask_pol="point-based-std", device="cuda", shared_base=False, batch_same_size=False,
-                     overlap=False, group_size=18, ms_ssim=False, writing=None, names=None):
+                     overlap=False, group_size=18, ms_ssim=False, writing=None, names=None, pixel_io=False):
     """images: iterable of [1,3,H,W] (or [3,H,W]) float tensors in [0,1].
     Returns (bpp[level], psnr[level], dec_time[level]) averaged over the images, as step.py:404 does,
     plus the per-image table.
@@ -133,12 +183,20 @@ def compress_with_ac(model, images, pr_list=None, mask_pol="point-based-std", de
 
     ms_ssim=True adds "ms_ssim" and "ms_ssim_db" to every row (step.py:350-353), in every path; the batched paths compute it with one
     launch set and one read-back per (group, level).  writing=<dir> implies ms_ssim=True and appends level_<j>_.txt files in the line
-    formats of step.py:373 and :402; images are named names[i], or by their index when names is None."""
+    formats of step.py:373 and :402; images are named names[i], or by their index when names is None.
+
+    pixel_io=True (plain and shared_base loops; with overlap or batch_same_size it raises NotImplementedError): an image may also be a
+    uint8 tensor ([3,H,W] / [1,3,H,W], the decoded file as it is), and every uint8 image goes through progressivecodec_amd.pixels:
+    padding is one to_model_input, and un-pad, clamp and the PSNR sum are one from_model_output(..., ref=image) per level -- the sum
+    of (x - clamp(x_hat))^2 in float64, so the PSNR agrees with the float path to rounding, not bitwise -- with one read-back per image
+    instead of one per level.  MS-SSIM still takes the float tensors.  A float image is coded exactly as without the switch."""
     import torch
     import torch.nn.functional as F
     pr_list = list(PR_LIST if pr_list is None else pr_list)
     ms_ssim = ms_ssim or writing is not None
     rows = []
+    if pixel_io and (overlap or batch_same_size):
+        raise NotImplementedError("pixel_io=True is wired into the plain and the shared_base loops only")
     if overlap:
         pipe = _pipeline_of(model)
         imgs = [(x if x.dim() == 4 else x.unsqueeze(0)) for x in images]
@@ -228,6 +286,9 @@ def compress_with_ac(model, images, pr_list=None, mask_pol="point-based-std", de
             x = x if x.dim() == 4 else x.unsqueeze(0)
             x = x.to(device)
             h, w = x.shape[2:]
+            if pixel_io and x.dtype == torch.uint8:
+                rows.extend(_pixel_io_rows(model, x, pr_list, mask_pol, shared_base, ms_ssim))
+                continue
             pad, unpad = compute_padding(h, w, 64)
             x_padded = F.pad(x, pad, mode="constant", value=0)
             if shared_base:
