@@ -5,7 +5,7 @@ sized tiles, the tiles are coded as a batch, and any rectangle of the image is d
   stitch          decoded tiles -> a window of the uint8 image (overlap bands blended) and, given the original, the distortion
                   sums behind PSNR, one kernel
   encode_tiled    uint8 image -> one PCT1 container: one PCB1 container (container.py) per tile behind an offset table
-  decode_tiled    PCT1 container -> uint8 image, or the region (y0, x0, h, w) of it from the tiles that cover it alone
+  decode_tiled    PCT1 / PCT2 container -> uint8 image, or the region (y0, x0, h, w) of it from the tiles that cover it alone
 
 Geometry.  Tile size T (a multiple of 64), overlap O (a multiple of 4, 0 <= O <= T/2), stride S = T - O.  An axis of length L has
 1 tile if L <= T, otherwise ceil((L - T) / S) + 1; tile i covers [i*S, i*S + T), the image sits at the top-left of the grid, tiles
@@ -28,9 +28,13 @@ byte ranges of the covering tiles only; inside each, PCB1's own property holds (
 A container cut off after tile k still decodes every region inside tiles 0 .. k.  ny and nx are redundant with H, W, T and O: a
 container whose grid is not the one pc_tiles_grid gives is refused.
 
+PCT2 (written by rate.encode_tiled_to_size): magic "PCT2", version 1, the header and the table exactly as
+above; every tile's PCB1 holds exactly ONE level, and tiles may differ in quality (they agree in mask policy and contract).
+
 Layouts: "hwc" is [H,W,3], "chw" is [3,H,W].  There is no CPU fallback: CPU tensors raise ValueError before any device call.
 Everything runs on the current stream of the tensor's device.  Out of scope: a level-major container (quality-progressive
-truncation across the whole image), per-tile qualities, tiling inside compress_with_ac and REM models.
+truncation across the whole image), tiling inside compress_with_ac and REM models.  Per-tile qualities under a byte budget are
+rate.py's (PCT2).
 """
 import collections
 import ctypes as C
@@ -52,6 +56,7 @@ CUT, STITCH = 0, 1                        # pc_tiles_plan's `op`
 PC_ERR_HIP = -6                           # pcodec.h
 
 MAGIC = b"PCT1"
+MAGIC2 = b"PCT2"                          # one level per tile, tiles may differ in quality
 VERSION = 1
 _HEAD = "<BIIIIIII"                       # version, contract id, H, W, T, O, ny, nx
 HEADER_BYTES = 4 + struct.calcsize(_HEAD)
@@ -270,14 +275,15 @@ def plan(op, u8, layout, f32, x0=0, ref=None, ref_layout=None):
 
 # -- PCT1 ----------------------------------------------------------------------------------------------------------------------------
 
-def pack_tiled(tile_bufs, H, W, tile, overlap, contract=None):
-    """The PCB1 containers of every tile of the grid, in tile order -> one PCT1 container."""
+def pack_tiled(tile_bufs, H, W, tile, overlap, contract=None, per_tile_levels=False):
+    """The PCB1 containers of every tile of the grid, in tile order -> one PCT1 container; per_tile_levels: a PCT2 container, whose
+    tiles hold one level each (checked by decode_tiled, not here)."""
     from . import container
     g = grid_of(H, W, tile, overlap)
     if len(tile_bufs) != g.ny * g.nx:
         raise ContainerError(f"{g.ny * g.nx} tile containers expected, got {len(tile_bufs)}")
     contract = container.build_contract_id() if contract is None else int(contract)
-    head = MAGIC + struct.pack(_HEAD, VERSION, contract, g.H, g.W, g.T, g.O, g.ny, g.nx)
+    head = (MAGIC2 if per_tile_levels else MAGIC) + struct.pack(_HEAD, VERSION, contract, g.H, g.W, g.T, g.O, g.ny, g.nx)
     off = len(head) + 16 * len(tile_bufs)
     table = []
     for b in tile_bufs:
@@ -287,11 +293,13 @@ def pack_tiled(tile_bufs, H, W, tile, overlap, contract=None):
 
 
 def parse_tiled(buf):
-    """-> dict(contract, grid (TileGrid, whole grid), table [(offset, length) per tile], payload_start).  Checks the header, the
-    geometry against pc_tiles_grid and that the whole table is there; a table entry is checked against the buffer when its tile is
-    asked for (tile_bytes), so that a container cut off inside its payload still gives the tiles it holds completely."""
-    if len(buf) < 4 or bytes(buf[:4]) != MAGIC:
-        raise ContainerError("not a PCT1 container")
+    """-> dict(magic (b"PCT1" or b"PCT2"), contract, grid (TileGrid, whole grid), table [(offset, length) per tile], payload_start).
+    Checks the header, the geometry against pc_tiles_grid and that the whole table is there; a table entry is checked against the
+    buffer when its tile is asked for (tile_bytes), so that a container cut off inside its payload still gives the tiles it holds
+    completely."""
+    magic = bytes(buf[:4])
+    if len(buf) < 4 or magic not in (MAGIC, MAGIC2):
+        raise ContainerError("not a PCT1 or PCT2 container")
     if len(buf) < HEADER_BYTES:
         raise ContainerError("truncated header")
     ver, contract, H, W, T, O, ny, nx = struct.unpack_from(_HEAD, buf, 4)
@@ -309,7 +317,7 @@ def parse_tiled(buf):
     if len(buf) < start:
         raise ContainerError("truncated tile table")
     flat = struct.unpack_from(f"<{2 * ny * nx}Q", buf, HEADER_BYTES)
-    return {"contract": contract, "grid": g, "table": list(zip(flat[0::2], flat[1::2])), "payload_start": start}
+    return {"magic": magic, "contract": contract, "grid": g, "table": list(zip(flat[0::2], flat[1::2])), "payload_start": start}
 
 
 def tile_bytes(buf, hd, t):
@@ -348,7 +356,8 @@ def encode_tiled(model, img, qualities, tile=512, overlap=0, mask_pol="point-bas
 
 
 def decode_tiled(model, buf, level=-1, region=None, layout="hwc", rounding="nearest", max_tiles_per_call=32):
-    """One level (index into the quality list, negative from the end) of a PCT1 container -> uint8 [h,w,3] ("hwc") or [3,h,w] ("chw")
+    """One level (index into the quality list, negative from the end) of a PCT1 container, or the one level every tile of a PCT2
+    container holds (level -1 or 0; tiles may differ in quality and are decoded grouped by it) -> uint8 [h,w,3] ("hwc") or [3,h,w] ("chw")
     on the model's device: region = (y0, x0, h, w) of the image, default all of it.  Only the tiles that cover the region are read,
     decoded (max_tiles_per_call at a time, one batch each) and stitched; of each, only the header, the base segment and that level's
     segment.  ContainerError, before the model is touched, for a corrupt or truncated container and for tiles that disagree with the
@@ -363,6 +372,9 @@ def decode_tiled(model, buf, level=-1, region=None, layout="hwc", rounding="near
     if step < 1:
         raise ValueError(f"max_tiles_per_call must be at least 1, got {max_tiles_per_call}")
     hd = parse_tiled(buf)
+    pct2 = hd["magic"] == MAGIC2
+    if pct2 and int(level) not in (-1, 0):
+        raise ContainerError(f"a PCT2 container holds one level per tile: level must be -1 or 0, got {level}")
     g = hd["grid"]
     window = _window((0, 0, g.H, g.W) if region is None else region, g.H, g.W)
     g = g.with_rect(g.covering(window))
@@ -370,6 +382,8 @@ def decode_tiled(model, buf, level=-1, region=None, layout="hwc", rounding="near
     if hd["contract"] != container.build_contract_id():
         raise ContainerError(f"container was coded under numeric contract 0x{hd['contract']:08x}, this decoder implements "
                              f"0x{container.build_contract_id():08x}: the streams are not interchangeable (DESIGN.md section 2)")
+    if pct2:
+        return stitch(_decode_per_tile_levels(model, blobs, g, step), g, window, layout=layout, rounding=rounding)
     per_tile, common = [], None
     for k, (tb, th) in enumerate(blobs):
         n = len(th["qualities"])
@@ -392,3 +406,37 @@ def decode_tiled(model, buf, level=-1, region=None, layout="hwc", rounding="near
         outs.append(model.decompress([ys, zs], shape, q, mask_pol)["x_hat"])
     x_hat = outs[0] if len(outs) == 1 else torch.cat(outs)
     return stitch(x_hat, g, window, layout=layout, rounding=rounding)
+
+
+def _decode_per_tile_levels(model, blobs, g, step):
+    """The tiles of a PCT2 region -> float32 [n,3,T,T]: every tile holds one level; the tiles are grouped by quality (ascending, tile
+    order within a group), each group is decoded step tiles at a time and scattered to the tiles' places.  ContainerError, before the
+    model is touched, for a tile with another number of levels and for tiles that differ in mask policy, latent shape or slices."""
+    import torch
+    from . import container
+    per_tile, groups, common = [], {}, None
+    for k, (tb, th) in enumerate(blobs):
+        if len(th["qualities"]) != 1:
+            raise ContainerError(f"tile {k} of the region holds {len(th['qualities'])} levels, a PCT2 tile holds exactly one")
+        strings, shape, qs, _, mask_pol = container.unpack(tb, levels=[0], expect_contract=False)       # checked by decode_tiled, once
+        key = (tuple(shape), mask_pol)
+        if common is None:
+            common = key
+        elif key != common:
+            raise ContainerError(f"tile {k} of the region was coded as {key}, its first tile as {common}")
+        per_tile.append(strings[0])
+        groups.setdefault(qs[0], []).append(k)
+    shape, mask_pol = common
+    x_hat = None
+    for q in sorted(groups):
+        idx = groups[q]
+        for a in range(0, len(idx), step):
+            part = idx[a:a + step]
+            chunk = [per_tile[k] for k in part]
+            ys = [[s[0][k][0] for s in chunk] for k in range(len(chunk[0][0]))]      # y_strings[slice][image]
+            zs = [s[1][0] for s in chunk]
+            out = model.decompress([ys, zs], shape, q, mask_pol)["x_hat"]
+            if x_hat is None:
+                x_hat = torch.empty((g.n,) + tuple(out.shape[1:]), dtype=out.dtype, device=out.device)
+            x_hat[torch.tensor(part, device=out.device)] = out
+    return x_hat
