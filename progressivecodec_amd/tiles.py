@@ -362,8 +362,6 @@ def decode_tiled(model, buf, level=-1, region=None, layout="hwc", rounding="near
     decoded (max_tiles_per_call at a time, one batch each) and stitched; of each, only the header, the base segment and that level's
     segment.  ContainerError, before the model is touched, for a corrupt or truncated container and for tiles that disagree with the
     grid or with each other; a region whose tiles are complete decodes whatever follows them."""
-    import torch
-    from . import container
     if layout not in LAYOUTS:
         raise ValueError(f"layout must be 'hwc' or 'chw', got {layout!r}")
     if rounding not in ROUNDINGS:
@@ -371,6 +369,17 @@ def decode_tiled(model, buf, level=-1, region=None, layout="hwc", rounding="near
     step = int(max_tiles_per_call)
     if step < 1:
         raise ValueError(f"max_tiles_per_call must be at least 1, got {max_tiles_per_call}")
+    x_hat, g, window = _decode_region_tiles(model, buf, level, region, step)
+    return stitch(x_hat, g, window, layout=layout, rounding=rounding)
+
+
+def _decode_region_tiles(model, buf, level, region, step):
+    """What decode_tiled (and frame_tiles.decode_frame_tiled, on the PCT1 / PCT2 container inside a PCG1 one) does up to the stitch:
+    one level of the tiles that cover region = (y0, x0, h, w) (None: the whole image) -> (x_hat float32 [n,3,T,T], the TileGrid whose
+    rectangle they are, the window as four ints), decoded step tiles at a time.  Every refusal is a ContainerError (a region outside
+    the image a ValueError) raised before the model is touched."""
+    import torch
+    from . import container
     hd = parse_tiled(buf)
     pct2 = hd["magic"] == MAGIC2
     if pct2 and int(level) not in (-1, 0):
@@ -383,7 +392,7 @@ def decode_tiled(model, buf, level=-1, region=None, layout="hwc", rounding="near
         raise ContainerError(f"container was coded under numeric contract 0x{hd['contract']:08x}, this decoder implements "
                              f"0x{container.build_contract_id():08x}: the streams are not interchangeable (DESIGN.md section 2)")
     if pct2:
-        return stitch(_decode_per_tile_levels(model, blobs, g, step), g, window, layout=layout, rounding=rounding)
+        return _decode_per_tile_levels(model, blobs, g, step), g, window
     per_tile, common = [], None
     for k, (tb, th) in enumerate(blobs):
         n = len(th["qualities"])
@@ -404,8 +413,7 @@ def decode_tiled(model, buf, level=-1, region=None, layout="hwc", rounding="near
         ys = [[s[0][k][0] for s in chunk] for k in range(ns)]              # y_strings[slice][image]
         zs = [s[1][0] for s in chunk]
         outs.append(model.decompress([ys, zs], shape, q, mask_pol)["x_hat"])
-    x_hat = outs[0] if len(outs) == 1 else torch.cat(outs)
-    return stitch(x_hat, g, window, layout=layout, rounding=rounding)
+    return (outs[0] if len(outs) == 1 else torch.cat(outs)), g, window
 
 
 def _decode_per_tile_levels(model, blobs, g, step):
