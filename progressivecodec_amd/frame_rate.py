@@ -1,0 +1,211 @@
+"""Rate-controlled tiled coding of YUV 4:2:0 frames (libpc_frame_rate.so, frame_rate_csrc/pc_frame_rate.h): one
+NV12 / I420 / P010 frame in at most N bytes, every tile at the level of the quality list that rate.allocate picks for it, judged in
+the frame's own codes.  The composition of rate.py (section 12: the allocator, PCT2) and frame_tiles.py (section 14: the cut, PCG1).
+
+  frame_tile_distortion        decoded tiles + the original frame -> the exact integer weighted squared error per tile and plane
+                               (Y, Cb, Cr codes at the format's bit depth, 4:2:0 chroma), one pass over the tiles on the GPU
+  encode_frame_tiled_to_size   frame -> (PCG1 container of at most target_bytes bytes holding a PCT2 container, FrameRatePlan);
+                               frame_tiles.decode_frame_tiled reads it
+
+Distortion.  A tile is judged by its OWN rendering: section 13's emit on the tile with its in-frame part as the picture, compared
+with the original's codes (P010: word >> 6).  A luma sample counts with the integer numerators ay * ax of the stitch's band weights
+over den = 2 * overlap (den = 1 without overlap), a chroma sample with cy * cx, cy(k) = (ay(2k) + ay(2k+1)) / 2: per sample of the
+frame they sum to den^2 exactly, so sum_t D_t / den^2 is the squared code error of the decoded frame where tiles do not overlap -- at
+overlap 0 exactly what frame_tiles.stitch_frame(..., ref=...) reports, per plane -- and bounds the blended error from above, up to
+the quantiser, where they do.
+
+There is no CPU fallback: CPU tensors raise ValueError before any device call.  Everything runs on the current stream of the tensor's
+device.  Out of scope: a target PSNR (the dual problem), batches of frames, 4:2:2 / 4:4:4 and other chroma sitings, perceptual
+metrics, compress_with_ac.
+"""
+import collections
+import ctypes as C
+import os
+
+from ._lib import ERRORS, PC_OK
+from .frame_tiles import HEADER_BYTES as FRAME_HEADER_BYTES
+from .frame_tiles import FrameTilesError, _one_frame, pack_frame_tiled
+from .frames import FORMATS, RANGES, UPSAMPLES, Frame, _check_enums, _frame_struct, coefficients
+from .rate import TABLE_ENTRY_BYTES, allocate
+from .tiles import HEADER_BYTES, TileGrid, _check_tiles, grid_of, pack_tiled
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+LIB_PATH = os.path.join(_HERE, "libpc_frame_rate.so")
+
+#: every symbol frame_rate_csrc/pc_frame_rate.h declares
+EXPORTS = ["pc_frame_rate_workspace_size", "pc_frame_rate_tile_sse", "pc_frame_rate_plan", "pc_frame_rate_strerror",
+           "pc_frame_rate_last_hip_error"]
+
+PC_ERR_HIP = -6                           # pcodec.h
+
+_lib = None
+_range = range                            # the functions below take a parameter of that name
+
+
+def lib():
+    global _lib
+    if _lib is None:
+        if not os.path.exists(LIB_PATH):
+            raise ImportError(f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
+                              "(hipcc --offload-arch=gfx950).  progressivecodec_amd has no CPU fallback.")
+        L = C.CDLL(LIB_PATH)
+        i64, vp, ci, cf, fp = C.c_int64, C.c_void_p, C.c_int, C.c_float, C.POINTER(Frame)
+        L.pc_frame_rate_workspace_size.restype = C.c_size_t
+        L.pc_frame_rate_workspace_size.argtypes = [ci, ci]
+        L.pc_frame_rate_tile_sse.argtypes = [vp, i64, i64, i64] + [ci] * 8 + [cf] * 5 + [fp, vp, C.c_size_t, vp, vp]
+        L.pc_frame_rate_plan.argtypes = [vp, i64, i64, i64, ci, ci, fp, C.POINTER(ci)]
+        L.pc_frame_rate_strerror.restype = C.c_char_p
+        L.pc_frame_rate_strerror.argtypes = [ci]
+        _lib = L
+    return _lib
+
+
+class FrameRateError(RuntimeError):
+    def __init__(self, code, where=""):
+        L = lib()
+        hip = L.pc_frame_rate_last_hip_error() if code == PC_ERR_HIP else 0
+        super().__init__(f"{where}: {ERRORS.get(code, code)} ({L.pc_frame_rate_strerror(code).decode()})" + (f" hipError={hip}" if hip else ""))
+
+
+#: what encode_frame_tiled_to_size decided: levels[t] (index into the quality list), rates[t][l] (bytes tile t costs at level l, its
+#: table entry included), dists[t][l] (plane_dists weighted by plane_weights), plane_dists[t][l] = [D_Y, D_Cb, D_Cr]
+#: (frame_tile_distortion), den (the weights' denominator per axis), container_bytes (the length of the container), predicted (the
+#: sum of the chosen dists) and sse[p] (the sum of the chosen plane_dists per plane: at overlap 0 the decoded frame's exact SSE)
+FrameRatePlan = collections.namedtuple("FrameRatePlan", "levels rates dists plane_dists den container_bytes predicted sse")
+
+
+def max_tile(fmt):
+    """the largest tile whose distortion sums fit 63 bits: T^4 (2^n - 1)^2 < 2^60"""
+    return 1024 if fmt == "p010" else 2048
+
+
+def frame_tile_distortion(x_hat_tiles, grid, ref, fmt, matrix="bt709", range="limited", first_tile=0):
+    """x_hat_tiles: float32 cuda [n,3,T,T], the decoded tiles first_tile .. first_tile + n - 1 of grid's row-major ny x nx grid (a
+    linear range, not a rectangle; grid's own rectangle is ignored; any tile / channel / row strides, unit stride along a row), ref: the
+    whole original H x W frame in `fmt` (frames.py's tuple of planes, any row strides) -> int64 cuda [n,3]: per tile and plane
+    [Y, Cb, Cr] the sum over the tile's samples inside the frame of weight * (code - refcode)^2, exact (pc_frame_rate.h).  A tile's
+    sums do not depend on which range it is part of."""
+    import torch
+    _check_enums(fmt, matrix, range)
+    g = TileGrid(*grid)
+    full = grid_of(g.H, g.W, g.T, g.O)
+    if (full.ny, full.nx) != (g.ny, g.nx):
+        raise ValueError(f"{g}: the grid of a {g.H}x{g.W} frame is {full.ny}x{full.nx}")
+    if g.T > max_tile(fmt):
+        raise ValueError(f"tile must be at most {max_tile(fmt)} for the distortion sums of {fmt!r} to fit 63 bits, got {g.T}")
+    x = x_hat_tiles
+    n = int(x.shape[0]) if torch.is_tensor(x) and x.dim() == 4 else 0
+    first_tile = int(first_tile)
+    if n < 1 or first_tile < 0 or first_tile + n > full.ny * full.nx:
+        raise ValueError(f"tiles {first_tile} .. {first_tile + n - 1} lie outside the {full.ny}x{full.nx} grid"
+                         if n else "x_hat_tiles must be a [n,3,T,T] tensor with n >= 1")
+    _check_tiles(x, full._replace(nty=1, ntx=n))
+    rts, rH, rW = _one_frame(ref, fmt, "ref")
+    if (rH, rW) != (g.H, g.W) or rts[0].device != x.device:
+        raise ValueError(f"ref must be the {g.H}x{g.W} frame on {x.device}, got {rH}x{rW} on {rts[0].device}")
+    if x.device.type != "cuda":
+        raise ValueError(f"x_hat_tiles must be on a GPU (there is no CPU fallback), got {x.device}")
+    if x.stride(3) != 1 or x.stride(2) < g.T or min(x.stride()[:2]) < 1:
+        x = x.contiguous()
+    k = coefficients(matrix)
+    L = lib()
+    rst = _frame_struct(rts)
+    with torch.cuda.device(x.device):
+        nbytes = L.pc_frame_rate_workspace_size(g.T, n)
+        ws = torch.empty(nbytes // 8, dtype=torch.int64, device=x.device)
+        out = torch.empty((n, 3), dtype=torch.int64, device=x.device)
+        rc = L.pc_frame_rate_tile_sse(x.data_ptr(), x.stride(0), x.stride(1), x.stride(2), g.H, g.W, g.T, g.O, first_tile, n,
+                                      FORMATS[fmt], RANGES[range], k.kr, k.kg, k.kb, k.ib, k.ir, C.byref(rst), ws.data_ptr(), nbytes,
+                                      out.data_ptr(), torch.cuda.current_stream(x.device).cuda_stream)
+    del rts
+    if rc != PC_OK:
+        raise FrameRateError(rc, "pc_frame_rate_tile_sse")
+    return out
+
+
+def plan(x_hat_tiles, ref, fmt, overlap=0):
+    """pc_frame_rate_plan for tensors (host only, nothing is launched or copied): True where frame_tile_distortion of exactly these
+    tensors with this overlap takes the wide-access path.  ref is a tuple of batched tensors ([1,...]) whose strides already fit a
+    frame."""
+    _check_enums(fmt)
+    x = x_hat_tiles
+    wide = C.c_int(-1)
+    rf = _frame_struct(ref)
+    rc = lib().pc_frame_rate_plan(x.data_ptr(), x.stride(0), x.stride(1), x.stride(2), int(overlap), FORMATS[fmt], C.byref(rf), C.byref(wide))
+    if rc != PC_OK:
+        raise FrameRateError(rc, "pc_frame_rate_plan")
+    return bool(wide.value)
+
+
+def encode_frame_tiled_to_size(model, planes, qualities, target_bytes, fmt, matrix="bt709", range="limited", upsample="linear", tile=512,
+                               overlap=0, mask_pol="point-based-std", plane_weights=(1, 1, 1), importance=None, max_tiles_per_call=32):
+    """frame -> (PCG1 container of at most target_bytes bytes, FrameRatePlan): every tile at the level of `qualities` that
+    rate.allocate picks from the bytes each level costs (the tile's single-level PCB1 container plus its table entry) and the
+    distortion it leaves (frame_tile_distortion of the tile decoded at that level, the planes weighted by plane_weights = (wY, wCb,
+    wCr), non-negative ints; the default is the total squared code error over all samples), optionally weighted by importance
+    ([ny][nx] or a flat list, one positive number per tile).  ValueError if even the cheapest level of every tile does not fit.  The
+    tiles are cut, coded at every level (compress_levels), decoded again (decompress_levels) and measured max_tiles_per_call at a
+    time, so a call holds at most max_tiles_per_call * (1 + len(qualities)) tile tensors on the device; neither the bytes nor the
+    plan depend on it.  The container holds a PCT2 container (one level per tile); frame_tiles.decode_frame_tiled reads it."""
+    import torch
+    from . import container, frame_tiles
+    qualities = [float(q) for q in qualities]
+    if not qualities:
+        raise ValueError("at least one level")
+    _check_enums(fmt, matrix, range, upsample)
+    step = int(max_tiles_per_call)
+    if step < 1:
+        raise ValueError(f"max_tiles_per_call must be at least 1, got {max_tiles_per_call}")
+    pw = list(plane_weights)
+    if len(pw) != 3 or any(isinstance(v, bool) or not isinstance(v, int) or v < 0 for v in pw) or not any(pw):
+        raise ValueError(f"plane_weights must be three non-negative ints, not all zero, got {plane_weights!r}")
+    target_bytes = int(target_bytes)
+    ts, H, W = _one_frame(planes, fmt, "planes")
+    g = grid_of(H, W, tile, overlap)
+    if g.T > max_tile(fmt):
+        raise ValueError(f"tile must be at most {max_tile(fmt)} for the distortion sums of {fmt!r} to fit 63 bits, got {g.T}")
+    n = g.ny * g.nx
+    if importance is not None:
+        importance = list(importance)
+        if importance and isinstance(importance[0], (list, tuple)):
+            importance = [v for row in importance for v in row]
+        if len(importance) != n:
+            raise ValueError(f"importance needs one number per tile of the {g.ny}x{g.nx} grid, got {len(importance)}")
+    k = coefficients(matrix)
+    dev = ts[0].device
+    src = _frame_struct(ts)
+    CL = frame_tiles.lib()
+    bufs, rates, plane_dists = [], [], []
+    for a in _range(0, n, step):
+        b = min(step, n - a)
+        with torch.cuda.device(dev):
+            x = torch.empty((b, 3, g.T, g.T), dtype=torch.float32, device=dev)
+            m0 = 0
+            while m0 < b:                                               # the linear range a .. a + b - 1, one piece per grid row
+                i, j = divmod(a + m0, g.nx)
+                m = min(b - m0, g.nx - j)
+                rc = CL.pc_frame_tiles_cut(C.byref(src), FORMATS[fmt], RANGES[range], UPSAMPLES[upsample], k.a, k.b, k.c, k.d, H, W, g.T,
+                                           g.O, i, j, 1, m, x[m0:].data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+                if rc != PC_OK:
+                    raise FrameTilesError(rc, "pc_frame_tiles_cut")
+                m0 += m
+        datas = model.compress_levels(x, qualities, mask_pol=mask_pol)
+        del x
+        strings = [d["strings"] for d in datas]
+        shape = datas[0]["shape"]
+        decoded = model.decompress_levels(strings, shape, qualities, mask_pol)
+        d = torch.stack([frame_tile_distortion(o["x_hat"], g, ts, fmt, matrix, range, a) for o in decoded], 1).tolist()     # [b][levels][3]
+        del decoded
+        for t in _range(b):
+            bufs.append([container.pack([strings[l]], shape, [q], image_size=(g.T, g.T), mask_pol=mask_pol, image_index=t)
+                         for l, q in enumerate(qualities)])
+            rates.append([TABLE_ENTRY_BYTES + len(p) for p in bufs[-1]])
+            plane_dists.append([[int(v) for v in row] for row in d[t]])
+    del ts
+    dists = [[pw[0] * v[0] + pw[1] * v[1] + pw[2] * v[2] for v in row] for row in plane_dists]
+    levels = allocate(rates, dists, target_bytes - FRAME_HEADER_BYTES - HEADER_BYTES, importance)
+    inner = pack_tiled([bufs[t][levels[t]] for t in _range(n)], g.H, g.W, g.T, g.O, per_tile_levels=True)
+    buf = pack_frame_tiled(inner, fmt, matrix, range, upsample)
+    sse = [sum(plane_dists[t][levels[t]][p] for t in _range(n)) for p in _range(3)]
+    return buf, FrameRatePlan(levels, rates, dists, plane_dists, 2 * g.O if g.O else 1, len(buf),
+                              sum(dists[t][levels[t]] for t in _range(n)), sse)
