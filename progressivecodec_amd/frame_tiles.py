@@ -21,8 +21,9 @@ one PCT1 or PCT2 container whose H, W are the frame's, unmodified (its table off
 tiles.decode_tiled of it gives the uint8 RGB rendering.
 
 There is no CPU fallback: CPU tensors raise ValueError before any device call.  Everything runs on the current stream of the tensor's
-device.  Rate control from YUV (a frame in at most N bytes, per-tile levels) is frame_rate.py's.  Out of scope: batches of frames in
-one call, 4:2:2 / 4:4:4 and other chroma sitings, compress_with_ac.
+device.  Rate control from YUV (a frame in at most N bytes, per-tile levels) is frame_rate.py's; sequences of frames (tiles of several
+frames in one codec call, static tiles coded once) are clips.py's.  Out of scope: 4:2:2 / 4:4:4 and other chroma sitings,
+compress_with_ac.
 """
 import ctypes as C
 import os
