@@ -30,7 +30,7 @@ is asked for, so a clip cut off inside its payload still gives every frame whose
 
 There is no CPU fallback: CPU tensors raise ValueError before any device call.  Everything runs on the current stream of the tensors'
 device.  Out of scope: a tolerance (lossy tile skip) and any inter-frame prediction, matching a tile against anything but the same tile
-of the previous frame, rate control over a clip, 4:2:2 / 4:4:4, compress_with_ac.
+of the previous frame, rate control over a clip (clip_rate.py), 4:2:2 / 4:4:4, compress_with_ac.
 """
 import collections
 import ctypes as C

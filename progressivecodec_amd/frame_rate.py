@@ -15,8 +15,8 @@ overlap 0 exactly what frame_tiles.stitch_frame(..., ref=...) reports, per plane
 the quantiser, where they do.
 
 There is no CPU fallback: CPU tensors raise ValueError before any device call.  Everything runs on the current stream of the tensor's
-device.  Sequences of frames are clips.py's (without rate control).  Out of scope: a target PSNR (the dual problem), rate control
-over a clip, 4:2:2 / 4:4:4 and other chroma sitings, perceptual metrics, compress_with_ac.
+device.  Sequences of frames are clips.py's (without rate control) and clip_rate.py's (a clip in at most N bytes).  Out of scope: a
+target PSNR (the dual problem), 4:2:2 / 4:4:4 and other chroma sitings, perceptual metrics, compress_with_ac.
 """
 import collections
 import ctypes as C
