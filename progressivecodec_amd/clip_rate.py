@@ -24,8 +24,9 @@ PCS2 is PCS1 (clips.py: header, table, payload rules) with the magic "PCS2" and 
 level; tiles may differ in quality.  What PCT2 is to PCT1.
 
 There is no CPU fallback: CPU tensors raise ValueError before any device call.  Everything runs on the current stream of the tensors'
-device.  Out of scope: per-frame byte caps and constant bitrate, a target PSNR (the dual problem), a tolerance (lossy tile skip),
-inter-frame prediction, batching the decode across frames.
+device.  Out of scope: per-frame byte caps and constant bitrate, a target PSNR (the dual problem), a tolerance inside
+encode_clip_to_size (clip_tol.py has it for clips.encode_clip; the reuse identity above does not hold under it), inter-frame
+prediction, batching the decode across frames.
 """
 import collections
 import ctypes as C

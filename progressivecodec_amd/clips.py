@@ -29,8 +29,9 @@ coded in: two entries are either equal or disjoint, anything else is refused.  A
 is asked for, so a clip cut off inside its payload still gives every frame whose tiles it holds completely.
 
 There is no CPU fallback: CPU tensors raise ValueError before any device call.  Everything runs on the current stream of the tensors'
-device.  Out of scope: a tolerance (lossy tile skip) and any inter-frame prediction, matching a tile against anything but the same tile
-of the previous frame, rate control over a clip (clip_rate.py), 4:2:2 / 4:4:4, compress_with_ac.
+device.  A tolerance (near-static tiles reused under an exact error bound) is clip_tol.py's, which produces this module's container.
+Out of scope: any inter-frame prediction, matching a tile against anything but the same tile of an earlier frame, rate control over
+a clip (clip_rate.py), 4:2:2 / 4:4:4, compress_with_ac.
 """
 import collections
 import ctypes as C
@@ -384,30 +385,14 @@ def frame_container(buf, k):
 
 # -- through the codec ---------------------------------------------------------------------------------------------------------------
 
-def encode_clip(model, frames, qualities, fmt, matrix="bt709", range="limited", upsample="linear", tile=512, overlap=0,
-                mask_pol="point-based-std", reuse=True, max_tiles_per_call=32):
-    """clip -> (PCS1 container (bytes), ClipPlan) holding every level of `qualities` for every tile of every frame.  With reuse, one
-    clip_changes and one device-to-host copy of its result say which tiles changed: source[0][t] = 0, source[f][t] = source[f-1][t]
-    where all three counts of (f-1, t) are zero, else f.  The work list -- every (f, t) with source[f][t] == f, in (f, t) order --
-    is chunked by max_tiles_per_call ACROSS frames, so a codec call is filled even where a frame has few tiles to code: per chunk one
-    cut launch per frame present in it into one batch buffer, then model.compress_levels, then container.pack per tile.
-    reuse=False codes every tile (no change kernel, no aliasing).  The bytes depend neither on max_tiles_per_call nor on how the
-    frames are laid out in memory; frame_container(buf, k) is frame_tiles.encode_frame_tiled of frame k."""
+def _encode_source(model, fs, g, source, qualities, fmt, matrix, range, upsample, mask_pol, step):
+    """encode_clip once the source table is known (clip_tol.encode_clip comes here with its own): fs[k] the planes of frame k as
+    batched views, everything checked -> (the PCS1 container, the number of coded tiles).  The work list -- every (f, t) with
+    source[f][t] == f, in (f, t) order -- is chunked by `step` across frames: per chunk one cut launch per frame present in it into
+    one batch buffer, then model.compress_levels, then container.pack per tile."""
     import torch
     from . import container
-    qualities = [float(q) for q in qualities]
-    _check_enums(fmt, matrix, range, upsample)
-    step = int(max_tiles_per_call)
-    if step < 1:
-        raise ValueError(f"max_tiles_per_call must be at least 1, got {max_tiles_per_call}")
-    fs, H, W = _clip_frames(frames, fmt)
-    g = _grid(H, W, tile, overlap)
     n, F = g.ny * g.nx, len(fs)
-    if reuse and F > 1:
-        counts = _clip_changes(fs, fmt, g, upsample, 0, n).cpu()
-        source = source_table((counts != 0).any(dim=2).tolist())
-    else:
-        source = [[f] * n for f in _range(F)]
     work = [(f, t) for f in _range(F) for t in _range(n) if source[f][t] == f]
     k = coefficients(matrix)
     dev = fs[0][0].device
@@ -432,8 +417,33 @@ def encode_clip(model, frames, qualities, fmt, matrix="bt709", range="limited", 
         strings = [d["strings"] for d in datas]
         for b, (f, t) in enumerate(chunk):
             blobs[f][t] = container.pack(strings, datas[0]["shape"], qualities, image_size=(g.T, g.T), mask_pol=mask_pol, image_index=b)
-    buf = pack_clip(blobs, source, g.H, g.W, g.T, g.O, fmt, matrix, range, upsample)
-    return buf, ClipPlan(source, len(work), F * n - len(work), len(buf))
+    return pack_clip(blobs, source, g.H, g.W, g.T, g.O, fmt, matrix, range, upsample), len(work)
+
+
+def encode_clip(model, frames, qualities, fmt, matrix="bt709", range="limited", upsample="linear", tile=512, overlap=0,
+                mask_pol="point-based-std", reuse=True, max_tiles_per_call=32):
+    """clip -> (PCS1 container (bytes), ClipPlan) holding every level of `qualities` for every tile of every frame.  With reuse, one
+    clip_changes and one device-to-host copy of its result say which tiles changed: source[0][t] = 0, source[f][t] = source[f-1][t]
+    where all three counts of (f-1, t) are zero, else f.  The work list -- every (f, t) with source[f][t] == f, in (f, t) order --
+    is chunked by max_tiles_per_call ACROSS frames, so a codec call is filled even where a frame has few tiles to code: per chunk one
+    cut launch per frame present in it into one batch buffer, then model.compress_levels, then container.pack per tile.
+    reuse=False codes every tile (no change kernel, no aliasing).  The bytes depend neither on max_tiles_per_call nor on how the
+    frames are laid out in memory; frame_container(buf, k) is frame_tiles.encode_frame_tiled of frame k."""
+    qualities = [float(q) for q in qualities]
+    _check_enums(fmt, matrix, range, upsample)
+    step = int(max_tiles_per_call)
+    if step < 1:
+        raise ValueError(f"max_tiles_per_call must be at least 1, got {max_tiles_per_call}")
+    fs, H, W = _clip_frames(frames, fmt)
+    g = _grid(H, W, tile, overlap)
+    n, F = g.ny * g.nx, len(fs)
+    if reuse and F > 1:
+        counts = _clip_changes(fs, fmt, g, upsample, 0, n).cpu()
+        source = source_table((counts != 0).any(dim=2).tolist())
+    else:
+        source = [[f] * n for f in _range(F)]
+    buf, n_coded = _encode_source(model, fs, g, source, qualities, fmt, matrix, range, upsample, mask_pol, step)
+    return buf, ClipPlan(source, n_coded, F * n - n_coded, len(buf))
 
 
 def _level_strings(tb, th, level, where):
