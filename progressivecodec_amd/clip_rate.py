@@ -30,12 +30,12 @@ prediction, batching the decode across frames.
 """
 import collections
 import ctypes as C
-import os
 import struct
 from fractions import Fraction
 
 from . import clips
-from ._lib import ERRORS, PC_OK
+from . import _imagelib
+from ._lib import PC_OK
 from .clips import ENTRY_BYTES, HEADER_BYTES, _HEAD, _clip_changes, _clip_frames, _cut_into, _frame_index, clip_tile_bytes, source_table
 from .container import ContainerError
 from .frame_rate import max_tile
@@ -44,45 +44,34 @@ from .frames import FORMATS, RANGES, UPSAMPLES, _MATRIX_ID, Frame, _check_enums,
 from .rate import allocate
 from .tiles import TileGrid, _check_tiles, grid_of, pack_tiled
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_HERE, "libpc_clip_rate.so")
+LIB_PATH = _imagelib.lib_path("clip_rate")
 
 #: every symbol clip_rate_csrc/pc_clip_rate.h declares
 EXPORTS = ["pc_clip_rate_workspace_size", "pc_clip_rate_sse_jobs", "pc_clip_rate_plan", "pc_clip_rate_strerror",
            "pc_clip_rate_last_hip_error"]
 
-PC_ERR_HIP = -6                           # pcodec.h
-
 MAGIC = b"PCS2"
 VERSION = 1
 
-_lib = None
 _range = range                            # the functions below take a parameter of that name
 
 
+def _prototypes():
+    i64, vp, ci, cf, fp = C.c_int64, C.c_void_p, C.c_int, C.c_float, C.POINTER(Frame)
+    return {
+        "pc_clip_rate_workspace_size": (C.c_size_t, [ci, ci]),
+        "pc_clip_rate_sse_jobs": (None, [vp, i64, i64, i64] + [ci] * 6 + [cf] * 5 + [fp, vp, ci, vp, ci, vp, C.c_size_t, vp, vp]),
+        "pc_clip_rate_plan": (None, [vp, i64, i64, i64, ci, ci, fp, ci, C.POINTER(ci)]),
+        "pc_clip_rate_strerror": (C.c_char_p, [ci]),
+    }
+
+
 def lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise ImportError(f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                              "(hipcc --offload-arch=gfx950).  progressivecodec_amd has no CPU fallback.")
-        L = C.CDLL(LIB_PATH)
-        i64, vp, ci, cf, fp = C.c_int64, C.c_void_p, C.c_int, C.c_float, C.POINTER(Frame)
-        L.pc_clip_rate_workspace_size.restype = C.c_size_t
-        L.pc_clip_rate_workspace_size.argtypes = [ci, ci]
-        L.pc_clip_rate_sse_jobs.argtypes = [vp, i64, i64, i64] + [ci] * 6 + [cf] * 5 + [fp, vp, ci, vp, ci, vp, C.c_size_t, vp, vp]
-        L.pc_clip_rate_plan.argtypes = [vp, i64, i64, i64, ci, ci, fp, ci, C.POINTER(ci)]
-        L.pc_clip_rate_strerror.restype = C.c_char_p
-        L.pc_clip_rate_strerror.argtypes = [ci]
-        _lib = L
-    return _lib
+    return _imagelib.load(LIB_PATH, _prototypes)
 
 
-class ClipRateError(RuntimeError):
-    def __init__(self, code, where=""):
-        L = lib()
-        hip = L.pc_clip_rate_last_hip_error() if code == PC_ERR_HIP else 0
-        super().__init__(f"{where}: {ERRORS.get(code, code)} ({L.pc_clip_rate_strerror(code).decode()})" + (f" hipError={hip}" if hip else ""))
+class ClipRateError(_imagelib.ImageLibError):
+    _lib, _prefix = staticmethod(lib), "pc_clip_rate"
 
 
 #: what encode_clip_to_size decided: source[f][t] (clips.ClipPlan's); items[i] = (f, t), the coded tiles in (f, t) order; weights[i]

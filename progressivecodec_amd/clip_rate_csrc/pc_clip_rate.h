@@ -6,14 +6,15 @@
  *
  * Kept apart from libpcodec.so and from the other image-side libraries (libpc_pixels.so, libpc_tiles.so, libpc_rate.so,
  * libpc_frames.so, libpc_frame_tiles.so, libpc_frame_rate.so, libpc_clips.so): nothing here is part of the codec's numeric contract,
- * byte strings or profiles, and no library of the image domain depends on another (the device code this one shares with
- * pc_frame_rate.hip -- plane loads, levels, the emit arithmetic, band numerators, the item, the reduction -- is restated in it).
+ * byte strings or profiles, and no library of the image domain links another (the device code this one shares with
+ * pc_frame_rate.hip -- plane loads, levels, the emit arithmetic, band numerators, the item, the reduction -- comes from the headers of
+ * image_csrc/).
  * Plain C, the conventions of pc_frame_rate.h: device pointers, int64 strides in ELEMENTS, status codes PC_OK / PC_ERR_* (pcodec.h),
  * `stream` is a hipStream_t passed as void* (NULL = default stream).  No call allocates device memory or synchronises the host: the
  * caller passes the workspace, and every launch is ordered on `stream`.  Every argument is checked before the first HIP call; a call
  * that returns PC_ERR_ARG has launched nothing.  All offsets are 64-bit.
  *
- * A frame (pc_cr_frame, the layout of pc_frame_rate.h's pc_fr_frame and of pc_frames.h's pc_frame member for member) is ONE picture
+ * A frame (pc_cr_frame: like pc_frame_rate.h's pc_fr_frame a typedef of the one record pc_frame, pc_yuv_frame.h) is ONE picture
  * of H x W luma samples with Hc x Wc chroma samples, Hc = ceil(H/2), Wc = ceil(W/2), as strided planes; the batch strides are ignored.
  *   PC_CR_NV12  Y (r, q) at y[r*y_row + q];  Cb (i, j) at u[i*u_row + 2j], Cr one element after it;  v is ignored.  8-bit codes.
  *   PC_CR_I420  Y as above;  Cb at u[i*u_row + j], Cr at v[i*v_row + j].  8-bit codes.
@@ -32,22 +33,16 @@
 #define PC_CLIP_RATE_H
 
 #include "pcodec.h"
+#include "pc_yuv_frame.h"
 
 #ifdef __cplusplus
 extern "C" {
 #endif
 
-enum { PC_CR_NV12 = 0, PC_CR_I420 = 1, PC_CR_P010 = 2 };
-enum { PC_CR_LIMITED = 0, PC_CR_FULL = 1 };
+enum { PC_CR_NV12 = PC_YUV_NV12, PC_CR_I420 = PC_YUV_I420, PC_CR_P010 = PC_YUV_P010 };
+enum { PC_CR_LIMITED = PC_YUV_LIMITED, PC_CR_FULL = PC_YUV_FULL };
 
-typedef struct pc_cr_frame {
-    void* y;
-    int64_t y_batch, y_row;     /* y_batch, u_batch, v_batch: ignored (one picture per record) */
-    void* u;                    /* NV12 / P010: the interleaved CbCr plane */
-    int64_t u_batch, u_row;
-    void* v;                    /* I420 only */
-    int64_t v_batch, v_row;
-} pc_cr_frame;
+typedef pc_frame pc_cr_frame;       /* pc_yuv_frame.h; y_batch, u_batch, v_batch: ignored (one picture per record) */
 
 /* Bytes of device workspace pc_clip_rate_sse_jobs needs: 24 bytes (three 64-bit sums) per block of 256 work items; a work item is
  * one row pair of one tile by eight tile-aligned columns, so a job has T*T/16 of them and T*T/4096 blocks.  0 for arguments the call

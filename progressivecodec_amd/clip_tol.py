@@ -31,51 +31,41 @@ inter-frame prediction, matching a tile against other tiles, 4:2:2 / 4:4:4.
 """
 import collections
 import ctypes as C
-import os
 from fractions import Fraction
 
 from . import clips
-from ._lib import ERRORS, PC_OK
+from . import _imagelib
+from ._lib import PC_OK
 from .clips import _clip_frames, _encode_source
 from .frames import FORMATS, UPSAMPLES, Frame, _check_enums, _frame_struct, bits_of
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_HERE, "libpc_clip_tol.so")
+LIB_PATH = _imagelib.lib_path("clip_tol")
 
 #: every symbol clip_tol_csrc/pc_clip_tol.h declares
 EXPORTS = ["pc_clip_tol_workspace_size", "pc_clip_tol_scan", "pc_clip_tol_plan", "pc_clip_tol_strerror", "pc_clip_tol_last_hip_error"]
 
-PC_ERR_HIP = -6                           # pcodec.h
 NO_MSE = 1 << 30                          # pc_clip_tol.h: the mse_q10 that never binds
 MAX_BITS = 10                             # P010
 
-_lib = None
 _range = range                            # the functions below take a parameter of that name
 
 
+def _prototypes():
+    vp, ci, fp, ip = C.c_void_p, C.c_int, C.POINTER(Frame), C.POINTER(C.c_int)
+    return {
+        "pc_clip_tol_workspace_size": (C.c_size_t, [ci, ci]),
+        "pc_clip_tol_scan": (None, [fp, vp] + [ci] * 7 + [ip, ip, ci, vp, C.c_size_t, vp, vp, vp]),
+        "pc_clip_tol_plan": (None, [ci, fp, ci, ci, ip]),
+        "pc_clip_tol_strerror": (C.c_char_p, [ci]),
+    }
+
+
 def lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise ImportError(f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                              "(hipcc --offload-arch=gfx950).  progressivecodec_amd has no CPU fallback.")
-        L = C.CDLL(LIB_PATH)
-        vp, ci, fp, ip = C.c_void_p, C.c_int, C.POINTER(Frame), C.POINTER(C.c_int)
-        L.pc_clip_tol_workspace_size.restype = C.c_size_t
-        L.pc_clip_tol_workspace_size.argtypes = [ci, ci]
-        L.pc_clip_tol_scan.argtypes = [fp, vp] + [ci] * 7 + [ip, ip, ci, vp, C.c_size_t, vp, vp, vp]
-        L.pc_clip_tol_plan.argtypes = [ci, fp, ci, ci, ip]
-        L.pc_clip_tol_strerror.restype = C.c_char_p
-        L.pc_clip_tol_strerror.argtypes = [ci]
-        _lib = L
-    return _lib
+    return _imagelib.load(LIB_PATH, _prototypes)
 
 
-class ClipTolError(RuntimeError):
-    def __init__(self, code, where=""):
-        L = lib()
-        hip = L.pc_clip_tol_last_hip_error() if code == PC_ERR_HIP else 0
-        super().__init__(f"{where}: {ERRORS.get(code, code)} ({L.pc_clip_tol_strerror(code).decode()})" + (f" hipError={hip}" if hip else ""))
+class ClipTolError(_imagelib.ImageLibError):
+    _lib, _prefix = staticmethod(lib), "pc_clip_tol"
 
 
 def _three(v, what):

@@ -9,14 +9,14 @@
  *
  * Kept apart from libpcodec.so and from the other image-side libraries (libpc_pixels.so, libpc_tiles.so, libpc_rate.so,
  * libpc_frames.so, libpc_frame_tiles.so, libpc_frame_rate.so, libpc_clips.so, libpc_clip_rate.so): nothing here is part of the
- * codec's numeric contract, byte strings or profiles, and no library of the image domain depends on another (the device code this one
- * shares with pc_clips.hip -- plane loads, word >> 6 for P010, the footprint, the item, the halo block -- and with pc_clip_rate.hip --
- * the device frame table -- is restated in it).  Plain C, the conventions of pc_clip_rate.h: device pointers, int64 strides in
+ * codec's numeric contract, byte strings or profiles, and no library of the image domain links another (the device code this one
+ * shares with pc_clips.hip -- plane loads, word >> 6 for P010, the item, the halo block -- comes from the headers of image_csrc/,
+ * DESIGN.md section 19).  Plain C, the conventions of pc_clip_rate.h: device pointers, int64 strides in
  * ELEMENTS, status codes PC_OK / PC_ERR_* (pcodec.h), `stream` is a hipStream_t passed as void* (NULL = default stream).  No call
  * allocates device memory or synchronises the host: the caller passes the workspace, and every launch is ordered on `stream`.  Every
  * argument is checked before the first HIP call; a call that returns PC_ERR_ARG has launched nothing.  All offsets are 64-bit.
  *
- * A frame (pc_ct_frame, the layout of pc_frames.h's pc_frame member for member) is ONE picture of H x W luma samples with Hc x Wc
+ * A frame (pc_ct_frame, a typedef of the one record pc_frame, pc_yuv_frame.h) is ONE picture of H x W luma samples with Hc x Wc
  * chroma samples, Hc = ceil(H/2), Wc = ceil(W/2), as strided planes; the batch strides are ignored.
  *   PC_CT_NV12  Y (r, q) at y[r*y_row + q];  Cb (i, j) at u[i*u_row + 2j], Cr one element after it;  v is ignored.  8-bit codes.
  *   PC_CT_I420  Y as above;  Cb at u[i*u_row + j], Cr at v[i*v_row + j].  8-bit codes.
@@ -49,23 +49,17 @@
 #define PC_CLIP_TOL_H
 
 #include "pcodec.h"
+#include "pc_yuv_frame.h"
 
 #ifdef __cplusplus
 extern "C" {
 #endif
 
-enum { PC_CT_NV12 = 0, PC_CT_I420 = 1, PC_CT_P010 = 2 };
-enum { PC_CT_NEAREST = 0, PC_CT_LINEAR = 1 };
+enum { PC_CT_NV12 = PC_YUV_NV12, PC_CT_I420 = PC_YUV_I420, PC_CT_P010 = PC_YUV_P010 };
+enum { PC_CT_NEAREST = PC_YUV_NEAREST, PC_CT_LINEAR = PC_YUV_LINEAR };
 enum { PC_CT_NO_MSE = 1 << 30 };
 
-typedef struct pc_ct_frame {
-    void* y;
-    int64_t y_batch, y_row;     /* y_batch, u_batch, v_batch: ignored (one picture per record) */
-    void* u;                    /* NV12 / P010: the interleaved CbCr plane */
-    int64_t u_batch, u_row;
-    void* v;                    /* I420 only */
-    int64_t v_batch, v_row;
-} pc_ct_frame;
+typedef pc_frame pc_ct_frame;       /* pc_yuv_frame.h; y_batch, u_batch, v_batch: ignored (one picture per record) */
 
 /* Bytes of device workspace pc_clip_tol_scan needs for a grid of n_tiles tiles: 72 bytes (nine 64-bit numbers: count, sse, maxabs
  * of three planes) per block, T*T/4096 + 1 blocks per tile -- a work item is one row pair of one tile by eight tile-aligned luma

@@ -36,24 +36,22 @@ a clip (clip_rate.py), 4:2:2 / 4:4:4, compress_with_ac.
 import collections
 import ctypes as C
 import operator
-import os
 import struct
 
-from ._lib import ERRORS, PC_OK
+from . import _imagelib
+from ._lib import PC_OK
 from .container import ContainerError
 from .frame_tiles import _admissible_window, _one_frame, pack_frame_tiled, stitch_frame
 from .frames import FORMATS, RANGES, UPSAMPLES, _MATRIX_ID, Frame, _check_enums, _frame_struct, _frame_view, _inv, bits_of, coefficients
 from .tiles import grid_of, pack_tiled
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_HERE, "libpc_clips.so")
+LIB_PATH = _imagelib.lib_path("clips")
 
 #: every symbol clips_csrc/pc_clips.h declares
 EXPORTS = ["pc_clips_changes_workspace_size", "pc_clips_tile_changes", "pc_clips_cut_list", "pc_clips_plan", "pc_clips_strerror",
            "pc_clips_last_hip_error"]
 
 CHANGES, CUT = 0, 1                       # pc_clips_plan's `op`
-PC_ERR_HIP = -6                           # pcodec.h
 MAX_TILE = 2048                           # pc_clips.h
 
 MAGIC = b"PCS1"
@@ -62,34 +60,26 @@ _HEAD = "<BBBBBBIIIIIIII"                 # version, fmt, matrix, range, upsampl
 HEADER_BYTES = 4 + struct.calcsize(_HEAD)
 ENTRY_BYTES = 16
 
-_lib = None
 _range = range                            # the functions below take a parameter of that name
 
 
+def _prototypes():
+    vp, ci, cf, fp = C.c_void_p, C.c_int, C.c_float, C.POINTER(Frame)
+    return {
+        "pc_clips_changes_workspace_size": (C.c_size_t, [ci, ci]),
+        "pc_clips_tile_changes": (None, [fp, fp] + [ci] * 8 + [vp, C.c_size_t, vp, vp]),
+        "pc_clips_cut_list": (None, [fp, ci, ci, ci, cf, cf, cf, cf] + [ci] * 4 + [vp, ci, vp, vp]),
+        "pc_clips_plan": (None, [ci, ci, fp, fp, vp, ci, C.POINTER(ci)]),
+        "pc_clips_strerror": (C.c_char_p, [ci]),
+    }
+
+
 def lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise ImportError(f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                              "(hipcc --offload-arch=gfx950).  progressivecodec_amd has no CPU fallback.")
-        L = C.CDLL(LIB_PATH)
-        vp, ci, cf, fp = C.c_void_p, C.c_int, C.c_float, C.POINTER(Frame)
-        L.pc_clips_changes_workspace_size.restype = C.c_size_t
-        L.pc_clips_changes_workspace_size.argtypes = [ci, ci]
-        L.pc_clips_tile_changes.argtypes = [fp, fp] + [ci] * 8 + [vp, C.c_size_t, vp, vp]
-        L.pc_clips_cut_list.argtypes = [fp, ci, ci, ci, cf, cf, cf, cf] + [ci] * 4 + [vp, ci, vp, vp]
-        L.pc_clips_plan.argtypes = [ci, ci, fp, fp, vp, ci, C.POINTER(ci)]
-        L.pc_clips_strerror.restype = C.c_char_p
-        L.pc_clips_strerror.argtypes = [ci]
-        _lib = L
-    return _lib
+    return _imagelib.load(LIB_PATH, _prototypes)
 
 
-class ClipsError(RuntimeError):
-    def __init__(self, code, where=""):
-        L = lib()
-        hip = L.pc_clips_last_hip_error() if code == PC_ERR_HIP else 0
-        super().__init__(f"{where}: {ERRORS.get(code, code)} ({L.pc_clips_strerror(code).decode()})" + (f" hipError={hip}" if hip else ""))
+class ClipsError(_imagelib.ImageLibError):
+    _lib, _prefix = staticmethod(lib), "pc_clips"
 
 
 #: what encode_clip decided: source[f][t] (the frame tile t of frame f was last coded in: f itself where it was coded for frame f),

@@ -6,14 +6,15 @@
  *
  * Kept apart from libpcodec.so and from the other image-side libraries (libpc_pixels.so, libpc_tiles.so, libpc_rate.so,
  * libpc_frames.so, libpc_frame_tiles.so, libpc_frame_rate.so): nothing here is part of the codec's numeric contract, byte strings or
- * profiles, and no library of the image domain depends on another (the device code this one shares with pc_frame_tiles.hip -- plane
- * loads, levels, the ingest arithmetic -- is restated in it).  Plain C, the conventions of pc_frame_rate.h: device pointers, int64
+ * profiles, and no library of the image domain links another (the device code this one shares with pc_frame_tiles.hip -- plane
+ * loads, levels, the ingest arithmetic -- comes from the headers of image_csrc/).  Plain C, the conventions of
+ * pc_frame_rate.h: device pointers, int64
  * strides in ELEMENTS, status codes PC_OK / PC_ERR_* (pcodec.h), `stream` is a hipStream_t passed as void* (NULL = default stream).
  * No call allocates device memory or synchronises the host: the caller passes the workspace, and every launch is ordered on
  * `stream`.  Every argument is checked before the first HIP call; a call that returns PC_ERR_ARG has launched nothing.  All offsets
  * are 64-bit.
  *
- * A frame (pc_cl_frame, the layout of pc_frames.h's pc_frame member for member) is ONE picture of H x W luma samples with Hc x Wc
+ * A frame (pc_cl_frame, a typedef of the one record pc_frame, pc_yuv_frame.h) is ONE picture of H x W luma samples with Hc x Wc
  * chroma samples, Hc = ceil(H/2), Wc = ceil(W/2), as strided planes; the batch strides are ignored.
  *   PC_CL_NV12  Y (r, q) at y[r*y_row + q];  Cb (i, j) at u[i*u_row + 2j], Cr one element after it;  v is ignored.  8-bit codes.
  *   PC_CL_I420  Y as above;  Cb at u[i*u_row + j], Cr at v[i*v_row + j].  8-bit codes.
@@ -37,24 +38,18 @@
 #define PC_CLIPS_H
 
 #include "pcodec.h"
+#include "pc_yuv_frame.h"
 
 #ifdef __cplusplus
 extern "C" {
 #endif
 
-enum { PC_CL_NV12 = 0, PC_CL_I420 = 1, PC_CL_P010 = 2 };
-enum { PC_CL_LIMITED = 0, PC_CL_FULL = 1 };
-enum { PC_CL_NEAREST = 0, PC_CL_LINEAR = 1 };
+enum { PC_CL_NV12 = PC_YUV_NV12, PC_CL_I420 = PC_YUV_I420, PC_CL_P010 = PC_YUV_P010 };
+enum { PC_CL_LIMITED = PC_YUV_LIMITED, PC_CL_FULL = PC_YUV_FULL };
+enum { PC_CL_NEAREST = PC_YUV_NEAREST, PC_CL_LINEAR = PC_YUV_LINEAR };
 enum { PC_CL_CHANGES = 0, PC_CL_CUT = 1 };
 
-typedef struct pc_cl_frame {
-    void* y;
-    int64_t y_batch, y_row;     /* y_batch, u_batch, v_batch: ignored (one picture per call) */
-    void* u;                    /* NV12 / P010: the interleaved CbCr plane */
-    int64_t u_batch, u_row;
-    void* v;                    /* I420 only */
-    int64_t v_batch, v_row;
-} pc_cl_frame;
+typedef pc_frame pc_cl_frame;       /* pc_yuv_frame.h; y_batch, u_batch, v_batch: ignored (one picture per record) */
 
 /* Bytes of device workspace pc_clips_tile_changes needs: 24 bytes (three 64-bit counts) per block, T*T/4096 + 1 blocks per tile:
  * a work item is one row pair of one tile by eight tile-aligned luma columns with the four chroma sample pairs of its 2 x 2 cells, a
@@ -76,7 +71,7 @@ PC_API int pc_clips_tile_changes(const pc_cl_frame* cur, const pc_cl_frame* prev
 
 /* dst[m][0..2][r][q] = (R, G, B) of luma pixel (Y, X) = (ti*S + r, tj*S + q) of the frame, (ti, tj) = (tiles[m] / nx, tiles[m] % nx),
  * where that pixel lies inside H x W, and +0.0f elsewhere: bit for bit what pc_frame_tiles_cut writes for the rectangle
- * (ti, tj, 1, 1) -- pc_frame_tiles.h's arithmetic, restated.  With C the Cb or Cr plane of codes of the WHOLE frame:
+ * (ti, tj, 1, 1) -- pc_frame_tiles.h's arithmetic.  With C the Cb or Cr plane of codes of the WHOLE frame:
  *   i0 = Y >> 1, i1 = i0 + 1 if Y is odd else i0 - 1, clamped to [0, Hc-1]; j0, j1 likewise from X and Wc;
  *   c16 = 9 C[i0,j0] + 3 C[i0,j1] + 3 C[i1,j0] + C[i1,j1]   (PC_CL_LINEAR)   or   16 C[i0,j0]   (PC_CL_NEAREST)  -- integers, exact;
  *   y' = float(Ycode - yo) / float(ys);  cb' = float(c16_b - 16 co) / float(16 cs);  cr' likewise;

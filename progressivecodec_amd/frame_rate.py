@@ -20,51 +20,40 @@ target PSNR (the dual problem), 4:2:2 / 4:4:4 and other chroma sitings, perceptu
 """
 import collections
 import ctypes as C
-import os
 
-from ._lib import ERRORS, PC_OK
+from . import _imagelib
+from ._lib import PC_OK
 from .frame_tiles import HEADER_BYTES as FRAME_HEADER_BYTES
 from .frame_tiles import FrameTilesError, _one_frame, pack_frame_tiled
 from .frames import FORMATS, RANGES, UPSAMPLES, Frame, _check_enums, _frame_struct, coefficients
 from .rate import TABLE_ENTRY_BYTES, allocate
 from .tiles import HEADER_BYTES, TileGrid, _check_tiles, grid_of, pack_tiled
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_HERE, "libpc_frame_rate.so")
+LIB_PATH = _imagelib.lib_path("frame_rate")
 
 #: every symbol frame_rate_csrc/pc_frame_rate.h declares
 EXPORTS = ["pc_frame_rate_workspace_size", "pc_frame_rate_tile_sse", "pc_frame_rate_plan", "pc_frame_rate_strerror",
            "pc_frame_rate_last_hip_error"]
 
-PC_ERR_HIP = -6                           # pcodec.h
-
-_lib = None
 _range = range                            # the functions below take a parameter of that name
 
 
+def _prototypes():
+    i64, vp, ci, cf, fp = C.c_int64, C.c_void_p, C.c_int, C.c_float, C.POINTER(Frame)
+    return {
+        "pc_frame_rate_workspace_size": (C.c_size_t, [ci, ci]),
+        "pc_frame_rate_tile_sse": (None, [vp, i64, i64, i64] + [ci] * 8 + [cf] * 5 + [fp, vp, C.c_size_t, vp, vp]),
+        "pc_frame_rate_plan": (None, [vp, i64, i64, i64, ci, ci, fp, C.POINTER(ci)]),
+        "pc_frame_rate_strerror": (C.c_char_p, [ci]),
+    }
+
+
 def lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise ImportError(f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                              "(hipcc --offload-arch=gfx950).  progressivecodec_amd has no CPU fallback.")
-        L = C.CDLL(LIB_PATH)
-        i64, vp, ci, cf, fp = C.c_int64, C.c_void_p, C.c_int, C.c_float, C.POINTER(Frame)
-        L.pc_frame_rate_workspace_size.restype = C.c_size_t
-        L.pc_frame_rate_workspace_size.argtypes = [ci, ci]
-        L.pc_frame_rate_tile_sse.argtypes = [vp, i64, i64, i64] + [ci] * 8 + [cf] * 5 + [fp, vp, C.c_size_t, vp, vp]
-        L.pc_frame_rate_plan.argtypes = [vp, i64, i64, i64, ci, ci, fp, C.POINTER(ci)]
-        L.pc_frame_rate_strerror.restype = C.c_char_p
-        L.pc_frame_rate_strerror.argtypes = [ci]
-        _lib = L
-    return _lib
+    return _imagelib.load(LIB_PATH, _prototypes)
 
 
-class FrameRateError(RuntimeError):
-    def __init__(self, code, where=""):
-        L = lib()
-        hip = L.pc_frame_rate_last_hip_error() if code == PC_ERR_HIP else 0
-        super().__init__(f"{where}: {ERRORS.get(code, code)} ({L.pc_frame_rate_strerror(code).decode()})" + (f" hipError={hip}" if hip else ""))
+class FrameRateError(_imagelib.ImageLibError):
+    _lib, _prefix = staticmethod(lib), "pc_frame_rate"
 
 
 #: what encode_frame_tiled_to_size decided: levels[t] (index into the quality list), rates[t][l] (bytes tile t costs at level l, its

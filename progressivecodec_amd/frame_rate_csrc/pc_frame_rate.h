@@ -6,13 +6,14 @@
  *
  * Kept apart from libpcodec.so and from the other image-side libraries (libpc_pixels.so, libpc_tiles.so, libpc_rate.so,
  * libpc_frames.so, libpc_frame_tiles.so): nothing here is part of the codec's numeric contract, byte strings or profiles, and no
- * library of the image domain depends on another (the device code this one shares with pc_frame_tiles.hip and pc_rate.hip is restated
- * in it).  Plain C, the conventions of pc_frame_tiles.h: device pointers, int64 strides in ELEMENTS, status codes PC_OK / PC_ERR_*
+ * library of the image domain links another (the device code this one shares with pc_frame_tiles.hip and pc_rate.hip comes from the
+ * headers of image_csrc/).  Plain C, the conventions of pc_frame_tiles.h: device pointers, int64 strides in
+ * ELEMENTS, status codes PC_OK / PC_ERR_*
  * (pcodec.h), `stream` is a hipStream_t passed as void* (NULL = default stream).  No call allocates device memory or synchronises the
  * host: the caller passes the workspace, and every launch is ordered on `stream`.  Every argument is checked before the first HIP
  * call; a call that returns PC_ERR_ARG has launched nothing.  All offsets are 64-bit.
  *
- * A frame (pc_fr_frame, the layout of pc_frames.h's pc_frame member for member) is ONE picture of H x W luma samples with Hc x Wc
+ * A frame (pc_fr_frame, a typedef of the one record pc_frame, pc_yuv_frame.h) is ONE picture of H x W luma samples with Hc x Wc
  * chroma samples, Hc = ceil(H/2), Wc = ceil(W/2), as strided planes; the batch strides are ignored.
  *   PC_FR_NV12  Y (r, q) at y[r*y_row + q];  Cb (i, j) at u[i*u_row + 2j], Cr one element after it;  v is ignored.  8-bit codes.
  *   PC_FR_I420  Y as above;  Cb at u[i*u_row + j], Cr at v[i*v_row + j].  8-bit codes.
@@ -33,22 +34,16 @@
 #define PC_FRAME_RATE_H
 
 #include "pcodec.h"
+#include "pc_yuv_frame.h"
 
 #ifdef __cplusplus
 extern "C" {
 #endif
 
-enum { PC_FR_NV12 = 0, PC_FR_I420 = 1, PC_FR_P010 = 2 };
-enum { PC_FR_LIMITED = 0, PC_FR_FULL = 1 };
+enum { PC_FR_NV12 = PC_YUV_NV12, PC_FR_I420 = PC_YUV_I420, PC_FR_P010 = PC_YUV_P010 };
+enum { PC_FR_LIMITED = PC_YUV_LIMITED, PC_FR_FULL = PC_YUV_FULL };
 
-typedef struct pc_fr_frame {
-    void* y;
-    int64_t y_batch, y_row;     /* y_batch, u_batch, v_batch: ignored (one picture per call) */
-    void* u;                    /* NV12 / P010: the interleaved CbCr plane */
-    int64_t u_batch, u_row;
-    void* v;                    /* I420 only */
-    int64_t v_batch, v_row;
-} pc_fr_frame;
+typedef pc_frame pc_fr_frame;       /* pc_yuv_frame.h; y_batch, u_batch, v_batch: ignored (one picture per record) */
 
 /* Bytes of device workspace pc_frame_rate_tile_sse needs: 24 bytes (three 64-bit sums) per block of 256 work items; a work item is
  * one row pair of one tile by eight tile-aligned columns, so a tile has T*T/16 of them and T*T/4096 blocks.  0 for arguments the

@@ -26,57 +26,46 @@ frames in one codec call, static tiles coded once) are clips.py's.  Out of scope
 compress_with_ac.
 """
 import ctypes as C
-import os
 import struct
 
-from ._lib import ERRORS, PC_OK
+from . import _imagelib
+from ._lib import PC_OK
 from .frames import (FORMATS, RANGES, UPSAMPLES, _MATRIX_ID, Distortion, Frame, _check_enums, _frame_struct, _frame_view, _inv, bits_of,
                      coefficients, empty_frame)
 from .tiles import TileGrid, _check_tiles, _window, grid_of
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_HERE, "libpc_frame_tiles.so")
+LIB_PATH = _imagelib.lib_path("frame_tiles")
 
 #: every symbol frame_tiles_csrc/pc_frame_tiles.h declares
 EXPORTS = ["pc_frame_tiles_cut", "pc_frame_tiles_stitch_workspace_size", "pc_frame_tiles_stitch", "pc_frame_tiles_plan",
            "pc_frame_tiles_strerror", "pc_frame_tiles_last_hip_error"]
 
 CUT, STITCH = 0, 1                        # pc_frame_tiles_plan's `op`
-PC_ERR_HIP = -6                           # pcodec.h
-
 MAGIC = b"PCG1"
 VERSION = 1
 _HEAD = "<BBBBBB"                         # version, fmt, matrix, range, upsample, bits
 HEADER_BYTES = 4 + struct.calcsize(_HEAD)
 
-_lib = None
 _range = range                            # the functions below take a parameter of that name
 
 
+def _prototypes():
+    i64, vp, ci, cf, fp = C.c_int64, C.c_void_p, C.c_int, C.c_float, C.POINTER(Frame)
+    return {
+        "pc_frame_tiles_cut": (None, [fp, ci, ci, ci, cf, cf, cf, cf] + [ci] * 8 + [vp, vp]),
+        "pc_frame_tiles_stitch_workspace_size": (C.c_size_t, [ci, ci, ci]),
+        "pc_frame_tiles_stitch": (None, [vp, i64, i64, i64] + [ci] * 14 + [cf] * 5 + [fp, fp, vp, C.c_size_t, vp, vp]),
+        "pc_frame_tiles_plan": (None, [ci, ci, fp, vp, i64, i64, i64, ci, ci, fp, C.POINTER(ci)]),
+        "pc_frame_tiles_strerror": (C.c_char_p, [ci]),
+    }
+
+
 def lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise ImportError(f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                              "(hipcc --offload-arch=gfx950).  progressivecodec_amd has no CPU fallback.")
-        L = C.CDLL(LIB_PATH)
-        i64, vp, ci, cf, fp = C.c_int64, C.c_void_p, C.c_int, C.c_float, C.POINTER(Frame)
-        L.pc_frame_tiles_cut.argtypes = [fp, ci, ci, ci, cf, cf, cf, cf] + [ci] * 8 + [vp, vp]
-        L.pc_frame_tiles_stitch_workspace_size.restype = C.c_size_t
-        L.pc_frame_tiles_stitch_workspace_size.argtypes = [ci, ci, ci]
-        L.pc_frame_tiles_stitch.argtypes = [vp, i64, i64, i64] + [ci] * 14 + [cf] * 5 + [fp, fp, vp, C.c_size_t, vp, vp]
-        L.pc_frame_tiles_plan.argtypes = [ci, ci, fp, vp, i64, i64, i64, ci, ci, fp, C.POINTER(ci)]
-        L.pc_frame_tiles_strerror.restype = C.c_char_p
-        L.pc_frame_tiles_strerror.argtypes = [ci]
-        _lib = L
-    return _lib
+    return _imagelib.load(LIB_PATH, _prototypes)
 
 
-class FrameTilesError(RuntimeError):
-    def __init__(self, code, where=""):
-        L = lib()
-        hip = L.pc_frame_tiles_last_hip_error() if code == PC_ERR_HIP else 0
-        super().__init__(f"{where}: {ERRORS.get(code, code)} ({L.pc_frame_tiles_strerror(code).decode()})" + (f" hipError={hip}" if hip else ""))
+class FrameTilesError(_imagelib.ImageLibError):
+    _lib, _prefix = staticmethod(lib), "pc_frame_tiles"
 
 
 def admissible(window, H, W):

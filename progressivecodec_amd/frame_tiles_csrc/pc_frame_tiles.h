@@ -6,13 +6,15 @@
  *
  * Kept apart from libpcodec.so and from the other image-side libraries (libpc_pixels.so, libpc_tiles.so, libpc_rate.so,
  * libpc_frames.so): nothing here is part of the codec's numeric contract, byte strings or profiles, and no library of the image domain
- * depends on another (the device code this one shares with pc_frames.hip and pc_tiles.hip is restated in it).  Plain C, the
+ * links another (the device code this one shares with pc_frames.hip and pc_tiles.hip comes from the headers of image_csrc/, DESIGN.md
+ * section 19).  Plain C, the
  * conventions of pc_frames.h and pc_tiles.h: device pointers, int64 strides, status codes PC_OK / PC_ERR_* (pcodec.h), `stream` is a
  * hipStream_t passed as void* (NULL = default stream).  No call allocates device memory or synchronises the host: the caller passes
  * the workspace, and every launch is ordered on `stream`.  Every argument is checked before the first HIP call; a call that returns
  * PC_ERR_ARG has launched nothing.  All offsets are 64-bit.
  *
- * A frame (pc_ft_frame, the layout of pc_frames.h's pc_frame) is ONE picture of H x W luma samples with Hc x Wc chroma samples,
+ * A frame (pc_ft_frame, a typedef of the one record pc_frame, pc_yuv_frame.h) is ONE picture of H x W luma samples with Hc x Wc chroma
+ * samples,
  * Hc = ceil(H/2), Wc = ceil(W/2), as strided planes; the batch strides are ignored.  Strides are in ELEMENTS: bytes for the 8-bit
  * formats, little-endian 16-bit words for PC_FT_P010.
  *   PC_FT_NV12  Y (r, q) at y[r*y_row + q];  Cb (i, j) at u[i*u_row + 2j], Cr one element after it;  v is ignored.  8-bit codes.
@@ -38,24 +40,18 @@
 #define PC_FRAME_TILES_H
 
 #include "pcodec.h"
+#include "pc_yuv_frame.h"
 
 #ifdef __cplusplus
 extern "C" {
 #endif
 
-enum { PC_FT_NV12 = 0, PC_FT_I420 = 1, PC_FT_P010 = 2 };
-enum { PC_FT_LIMITED = 0, PC_FT_FULL = 1 };
-enum { PC_FT_NEAREST = 0, PC_FT_LINEAR = 1 };
+enum { PC_FT_NV12 = PC_YUV_NV12, PC_FT_I420 = PC_YUV_I420, PC_FT_P010 = PC_YUV_P010 };
+enum { PC_FT_LIMITED = PC_YUV_LIMITED, PC_FT_FULL = PC_YUV_FULL };
+enum { PC_FT_NEAREST = PC_YUV_NEAREST, PC_FT_LINEAR = PC_YUV_LINEAR };
 enum { PC_FT_CUT = 0, PC_FT_STITCH = 1 };
 
-typedef struct pc_ft_frame {
-    void* y;
-    int64_t y_batch, y_row;     /* y_batch, u_batch, v_batch: ignored (one picture per call) */
-    void* u;                    /* NV12 / P010: the interleaved CbCr plane */
-    int64_t u_batch, u_row;
-    void* v;                    /* I420 only */
-    int64_t v_batch, v_row;
-} pc_ft_frame;
+typedef pc_frame pc_ft_frame;       /* pc_yuv_frame.h; y_batch, u_batch, v_batch: ignored (one picture per record) */
 
 /* dst[a*ntx + b][0..2][r][q] = (R, G, B) of luma pixel (Y, X) = ((ty0 + a)*S + r, (tx0 + b)*S + q) of the frame where that pixel
  * lies inside H x W, and +0.0f elsewhere.  With C the Cb or Cr plane of codes of the WHOLE frame:

@@ -1,6 +1,7 @@
 // pc_frame_tiles.hip -- one YUV 4:2:0 frame (NV12 / I420 / P010) <-> independent tiles of float32 RGB planes on gfx950
-// (pc_frame_tiles.h).  Definition: DESIGN.md section 14, the composition of sections 13 and 11; the device code shared with
-// pc_frames.hip (loads, levels, to_rgb, the emit arithmetic) and pc_tiles.hip (geometry, quotient, the blend) is restated here.
+// (pc_frame_tiles.h).  Definition: DESIGN.md section 14, the composition of sections 13 and 11; the cut is cut_item of
+// image_csrc/pc_yuv_items.h, as in pc_frames.hip and pc_clips.hip; loads, levels and the emit arithmetic are
+// image_csrc/pc_yuv_device.h's, the geometry image_csrc/pc_tile_grid.h's, the reduction image_csrc/pc_reduce.h's.
 //
 // A work item is eight consecutive luma columns: of ONE tile row for the cut (aligned in tile columns; its two chroma rows are chosen
 // per luma row), of one ROW PAIR of the window for the stitch (aligned to a multiple of 8 in FRAME columns; four chroma samples, each
@@ -11,91 +12,21 @@
 // path (WIDE: four elements of a plane and four floats per access; else one by one) only changes the load and store instructions,
 // never which thread handles which sample or in which order it adds: the bits are the same on both.  No LDS on the data path; the
 // sums go thread, wave tree, waves in order (12 words of LDS), then final_kernel over the block partials, no atomics.
-#include <hip/hip_runtime.h>
+#include <climits>
 
-#include <atomic>
-#include <cstdint>
+#include "pc_image_host.h"
+#include "pc_reduce.h"
+#include "pc_tile_grid.h"
+#include "pc_yuv_device.h"
+#include "pc_yuv_items.h"
 
 #include "pc_frame_tiles.h"
 
-static std::atomic<int> g_last_hip{0};
-#define HIPCHK(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { g_last_hip = (int)_e; return PC_ERR_HIP; } } while (0)
-
 namespace {
-
-constexpr int NT = 256;                  // threads per block (4 waves)
-constexpr int COLS = 8;                  // luma columns per work item
-
-template <class T>
-struct Planes {                          // pc_ft_frame with typed pointers; row strides in elements
-    T* y;
-    int64_t yr;
-    T* u;
-    int64_t ur;
-    T* v;
-    int64_t vr;
-};
-
-struct Levels {
-    int yo, ys, co, cs, maxv;
-};
-
-struct IngestCoef {
-    float a, b, c, d;
-};
-
-struct EmitCoef {
-    float kr, kg, kb, ib, ir;
-};
-
-struct F32 {                             // a float tile set, strides in elements
-    const float* p;
-    int64_t st, sc, sh;
-};
 
 struct Tiling {                          // the grid and the rectangle a tile set holds
     int T, S, O, ny, nx, ty0, tx0, ntx;
 };
-
-inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
-
-// four consecutive elements of a plane in one access: a 32-bit word of bytes, a 64-bit word of 16-bit words
-__device__ __forceinline__ void load4(const uint8_t* p, unsigned v[4])
-{
-    const uint32_t w = *reinterpret_cast<const uint32_t*>(p);
-    v[0] = w & 255u; v[1] = (w >> 8) & 255u; v[2] = (w >> 16) & 255u; v[3] = w >> 24;
-}
-
-__device__ __forceinline__ void load4(const uint16_t* p, unsigned v[4])
-{
-    const uint2 w = *reinterpret_cast<const uint2*>(p);
-    v[0] = w.x & 0xffffu; v[1] = w.x >> 16; v[2] = w.y & 0xffffu; v[3] = w.y >> 16;
-}
-
-__device__ __forceinline__ void store4(uint8_t* p, const unsigned v[4])
-{
-    *reinterpret_cast<uint32_t*>(p) = v[0] | (v[1] << 8) | (v[2] << 16) | (v[3] << 24);
-}
-
-__device__ __forceinline__ void store4(uint16_t* p, const unsigned v[4])
-{
-    *reinterpret_cast<uint2*>(p) = make_uint2(v[0] | (v[1] << 16), v[2] | (v[3] << 16));
-}
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
-
-__device__ __forceinline__ float clamp01(float v) { return fminf(fmaxf(v, 0.f), 1.f); }
-
-// One luma pixel of the ingest: its code and the two 16-fold chroma sums -> R, G, B.
-__device__ __forceinline__ void to_rgb(int Y, int cb16, int cr16, const Levels& lv, const IngestCoef& k, float& R, float& G, float& B)
-{
-    const float y = (float)(Y - lv.yo) / (float)lv.ys;
-    const float cb = (float)(cb16 - 16 * lv.co) / (float)(16 * lv.cs);
-    const float cr = (float)(cr16 - 16 * lv.co) / (float)(16 * lv.cs);
-    R = clamp01(y + cr * k.a);
-    G = clamp01((y - cb * k.b) - cr * k.c);
-    B = clamp01(y + cb * k.d);
-}
 
 // Items are the eight-column groups of the tiles' rows: item -> (tile t of the rectangle, row r, group g), tile columns 8g .. 8g+7.
 // G8 = T / 8, tile_items = T * G8, items = nty * ntx * tile_items.  SH: the bits below the code in an element (P010: 6).  The chroma
@@ -104,8 +35,6 @@ template <class T, bool IL, bool WIDE>
 __global__ __launch_bounds__(NT) void cut_kernel(Planes<const T> s, int H, int W, int Hc, int Wc, Tiling tg, float* __restrict__ dst, int G8,
                                                  int tile_items, int64_t items, int linear, Levels lv, IngestCoef k)
 {
-    constexpr int SH = sizeof(T) == 2 ? 6 : 0;
-    constexpr int CS = IL ? 2 : 1;                                // elements from one Cb (Cr) sample to the next
     const int64_t item = (int64_t)blockIdx.x * NT + threadIdx.x;
     if (item >= items) return;
     const int t = (int)(item / tile_items), rem = (int)(item - (int64_t)t * tile_items);
@@ -117,93 +46,10 @@ __global__ __launch_bounds__(NT) void cut_kernel(Planes<const T> s, int H, int W
     for (int c = 0; c < 3; ++c)
 #pragma unroll
         for (int i = 0; i < COLS; ++i) o[c][i] = 0.f;
-    if (Y64 < H && X64 < W) {
-        const int y = (int)Y64, x0 = (int)X64;
-        const int i0 = y >> 1;
-        const int i1 = clampi(i0 + ((y & 1) ? 1 : -1), 0, Hc - 1);
-        const T* yrow = s.y + (int64_t)y * s.yr;
-        const T* u0 = s.u + (int64_t)i0 * s.ur;                   // Cb of chroma row i0, i1; Cr: one element on, or the V plane
-        const T* u1 = s.u + (int64_t)i1 * s.ur;
-        const T* v0 = IL ? u0 + 1 : s.v + (int64_t)i0 * s.vr;
-        const T* v1 = IL ? u1 + 1 : s.v + (int64_t)i1 * s.vr;
-        if (WIDE && x0 + COLS - 1 < W) {                          // x0 is a multiple of 8 here
-            unsigned Yc[COLS];
-            load4(yrow + x0, Yc);
-            load4(yrow + x0 + 4, Yc + 4);
-            const int jc = x0 >> 1;                                // chroma columns jc .. jc+3 exist; a multiple of 4
-            const int jl = max(jc - 1, 0), jr = min(jc + 4, Wc - 1);
-            unsigned cw[2][2][6];                                  // [row i0, i1][Cb, Cr][columns jl, jc .. jc+3, jr]
-#pragma unroll
-            for (int rr = 0; rr < 2; ++rr) {
-                const T* pu = rr ? u1 : u0;
-                const T* pv = rr ? v1 : v0;
-                if (rr == 1 && !linear) {
-#pragma unroll
-                    for (int j = 0; j < 6; ++j) { cw[1][0][j] = cw[0][0][j]; cw[1][1][j] = cw[0][1][j]; }
-                    break;
-                }
-                if (IL) {
-                    unsigned e[8];
-                    load4(pu + 2 * (int64_t)jc, e);
-                    load4(pu + 2 * (int64_t)jc + 4, e + 4);
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) { cw[rr][0][1 + j] = e[2 * j]; cw[rr][1][1 + j] = e[2 * j + 1]; }
-                } else {
-                    load4(pu + jc, &cw[rr][0][1]);
-                    load4(pv + jc, &cw[rr][1][1]);
-                }
-                cw[rr][0][0] = pu[CS * (int64_t)jl]; cw[rr][1][0] = pv[CS * (int64_t)jl];
-                cw[rr][0][5] = pu[CS * (int64_t)jr]; cw[rr][1][5] = pv[CS * (int64_t)jr];
-            }
-#pragma unroll
-            for (int i = 0; i < COLS; ++i) {
-                const int j0 = 1 + (i >> 1), j1 = (i & 1) ? j0 + 1 : j0 - 1;
-                int c16[2];
-#pragma unroll
-                for (int p = 0; p < 2; ++p) {
-                    const int c00 = (int)(cw[0][p][j0] >> SH), c01 = (int)(cw[0][p][j1] >> SH);
-                    const int c10 = (int)(cw[1][p][j0] >> SH), c11 = (int)(cw[1][p][j1] >> SH);
-                    c16[p] = linear ? 9 * c00 + 3 * c01 + 3 * c10 + c11 : 16 * c00;
-                }
-                to_rgb((int)(Yc[i] >> SH), c16[0], c16[1], lv, k, o[0][i], o[1][i], o[2][i]);
-            }
-        } else {                                                  // element by element; also the items that straddle the right edge
-#pragma unroll
-            for (int i = 0; i < COLS; ++i) {
-                const int x = x0 + i;
-                if (x < W) {
-                    const int64_t j0 = x >> 1;
-                    const int64_t j1 = clampi((int)j0 + ((x & 1) ? 1 : -1), 0, Wc - 1);
-                    int c16[2];
-#pragma unroll
-                    for (int p = 0; p < 2; ++p) {
-                        const T* r0 = p ? v0 : u0;
-                        const T* r1 = p ? v1 : u1;
-                        const int c00 = (int)(r0[CS * j0] >> SH);
-                        if (linear) {
-                            const int c01 = (int)(r0[CS * j1] >> SH), c10 = (int)(r1[CS * j0] >> SH), c11 = (int)(r1[CS * j1] >> SH);
-                            c16[p] = 9 * c00 + 3 * c01 + 3 * c10 + c11;
-                        } else {
-                            c16[p] = 16 * c00;
-                        }
-                    }
-                    to_rgb((int)(yrow[x] >> SH), c16[0], c16[1], lv, k, o[0][i], o[1][i], o[2][i]);
-                }
-            }
-        }
-    }
+    if (Y64 < H && X64 < W) cut_item<T, IL, WIDE, false>(s, W, Hc, Wc, (int)Y64, (int)X64, linear, lv, k, o);
     const int64_t plane = (int64_t)tg.T * tg.T;
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        float* d = dst + ((int64_t)t * 3 + c) * plane + (int64_t)r * tg.T + COLS * g;
-        if (WIDE) {
-            *reinterpret_cast<float4*>(d) = make_float4(o[c][0], o[c][1], o[c][2], o[c][3]);
-            *reinterpret_cast<float4*>(d + 4) = make_float4(o[c][4], o[c][5], o[c][6], o[c][7]);
-        } else {
-#pragma unroll
-            for (int i = 0; i < COLS; ++i) d[i] = o[c][i];
-        }
-    }
+    for (int c = 0; c < 3; ++c) store8<WIDE>(dst + ((int64_t)t * 3 + c) * plane + (int64_t)r * tg.T + COLS * g, o[c], COLS);
 }
 
 // num / den for two small integers as the correctly rounded float32 quotient: both are exact doubles, the double quotient carries
@@ -304,24 +150,15 @@ __device__ __forceinline__ void stitch_item(const F32& x, const Tiling& tg, int 
 #pragma unroll
     for (int r = 0; r < 2; ++r) {
 #pragma unroll
-        for (int q = 0; q < COLS; ++q) {
-            const float R = clamp01(m[r][0][q]), Gc = clamp01(m[r][1][q]), Bc = clamp01(m[r][2][q]);
-            const float Yf = (k.kr * R + k.kg * Gc) + k.kb * Bc;
-            const float Cb = (Bc - Yf) * k.ib, Cr = (R - Yf) * k.ir;
-            yq[r][q] = (unsigned)clampi((int)rintf(Yf * (float)lv.ys + (float)lv.yo), 0, lv.maxv);
-            ub[r][q] = Cb * (float)lv.cs;
-            ur[r][q] = Cr * (float)lv.cs;
-        }
+        for (int q = 0; q < COLS; ++q) emit_px(m[r][0][q], m[r][1][q], m[r][2][q], lv, k, yq[r][q], ub[r][q], ur[r][q]);
     }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const bool two = FULL || 2 * j + 1 < hi;                   // else the window's odd last column stands in for the one right of it
         const float b01 = two ? ub[0][2 * j + 1] : ub[0][2 * j], b11 = two ? ub[1][2 * j + 1] : ub[1][2 * j];
         const float r01 = two ? ur[0][2 * j + 1] : ur[0][2 * j], r11 = two ? ur[1][2 * j + 1] : ur[1][2 * j];
-        const float mb = ((ub[0][2 * j] + b01) + (ub[1][2 * j] + b11)) * 0.25f + (float)lv.co;
-        const float mr = ((ur[0][2 * j] + r01) + (ur[1][2 * j] + r11)) * 0.25f + (float)lv.co;
-        cq[0][j] = (unsigned)clampi((int)rintf(mb), 0, lv.maxv);
-        cq[1][j] = (unsigned)clampi((int)rintf(mr), 0, lv.maxv);
+        cq[0][j] = (unsigned)emit_chroma(ub[0][2 * j], b01, ub[1][2 * j], b11, lv);
+        cq[1][j] = (unsigned)emit_chroma(ur[0][2 * j], r01, ur[1][2 * j], r11, lv);
     }
     const int64_t ci = yw >> 1, cx = xw >> 1;                      // the window's chroma row, and first chroma column (xw is even)
     if (dst.y) {
@@ -426,7 +263,6 @@ template <class T, bool IL, bool WIDE, bool HAS_REF>
 __global__ __launch_bounds__(NT) void stitch_kernel(F32 x, Tiling tg, int y0, int x0, int h, int w, Planes<T> dst, Planes<const T> ref,
                                                     int G, int items, Levels lv, EmitCoef k, unsigned long long* __restrict__ partials)
 {
-    __shared__ unsigned long long red[NT / 64][3];
     const int item = blockIdx.x * NT + threadIdx.x;
     unsigned long long su[3] = {0ull, 0ull, 0ull};
     if (item < items) {
@@ -439,103 +275,16 @@ __global__ __launch_bounds__(NT) void stitch_kernel(F32 x, Tiling tg, int y0, in
         else
             stitch_item<T, IL, WIDE, false, HAS_REF>(x, tg, y0 + 2 * i, dy, X0, lo, hi, 2 * i, X0 - x0, dst, ref, lv, k, su);
     }
-    if (HAS_REF) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1)
-#pragma unroll
-            for (int p = 0; p < 3; ++p) su[p] += __shfl_down(su[p], off, 64);
-        if ((threadIdx.x & 63) == 0)
-#pragma unroll
-            for (int p = 0; p < 3; ++p) red[threadIdx.x >> 6][p] = su[p];
-        __syncthreads();
-        if (threadIdx.x < 3) {
-            unsigned long long a = red[0][threadIdx.x];
-            for (int wv = 1; wv < NT / 64; ++wv) a += red[wv][threadIdx.x];
-            partials[(int64_t)blockIdx.x * 3 + threadIdx.x] = a;
-        }
-    }
+    if (HAS_REF) block_reduce<Sum>(su, partials + (int64_t)blockIdx.x * 3);
 }
 
 // One block: the block partials in a fixed order (thread t takes t, t + NT, ...; wave tree; waves in order).
 __global__ __launch_bounds__(NT) void final_kernel(const unsigned long long* __restrict__ partials, int blocks,
                                                    unsigned long long* __restrict__ sse)
 {
-    __shared__ unsigned long long red[NT / 64][3];
     unsigned long long su[3] = {0ull, 0ull, 0ull};
-    for (int t = threadIdx.x; t < blocks; t += NT)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) su[c] += partials[(int64_t)t * 3 + c];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) su[c] += __shfl_down(su[c], off, 64);
-    if ((threadIdx.x & 63) == 0)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) red[threadIdx.x >> 6][c] = su[c];
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        unsigned long long a = red[0][threadIdx.x];
-        for (int wv = 1; wv < NT / 64; ++wv) a += red[wv][threadIdx.x];
-        sse[threadIdx.x] = a;
-    }
-}
-
-bool fmt_ok(int fmt) { return fmt == PC_FT_NV12 || fmt == PC_FT_I420 || fmt == PC_FT_P010; }
-bool interleaved(int fmt) { return fmt != PC_FT_I420; }
-int elem_bytes(int fmt) { return fmt == PC_FT_P010 ? 2 : 1; }
-
-bool levels_of(int fmt, int range, Levels& lv)
-{
-    const int n = fmt == PC_FT_P010 ? 10 : 8, s = 1 << (n - 8), maxv = (1 << n) - 1;
-    if (range == PC_FT_LIMITED) lv = Levels{16 * s, 219 * s, 128 * s, 224 * s, maxv};
-    else if (range == PC_FT_FULL) lv = Levels{0, maxv, 128 * s, maxv, maxv};
-    else return false;
-    return true;
-}
-
-// One plane of rows of `len` elements: pointer aligned to its element, the row stride at least the row.
-bool plane_ok(const void* p, int64_t sr, int es, int64_t len) { return p && reinterpret_cast<uintptr_t>(p) % es == 0 && sr >= len; }
-
-bool frame_ok(int fmt, const pc_ft_frame* f, int W)
-{
-    if (!f || !fmt_ok(fmt)) return false;
-    const int es = elem_bytes(fmt);
-    const int64_t Wc = cdiv(W, 2);
-    if (!plane_ok(f->y, f->y_row, es, W)) return false;
-    if (interleaved(fmt)) return plane_ok(f->u, f->u_row, es, 2 * Wc);
-    return plane_ok(f->u, f->u_row, es, Wc) && plane_ok(f->v, f->v_row, es, Wc);
-}
-
-int64_t axis_tiles(int L, int T, int S) { return L <= T ? 1 : cdiv((int64_t)L - T, S) + 1; }
-
-// The geometry every call shares (pc_frame_tiles.h): T, O in range and the grid of an H x W frame within 32 bits.
-struct Geo {
-    int S, ny, nx;
-};
-
-bool geo_of(int H, int W, int T, int O, Geo& g)
-{
-    if (H < 1 || W < 1 || T < 64 || T % 64 || O < 0 || O % 4 || O > T / 2) return false;
-    const int S = T - O;
-    const int64_t ny = axis_tiles(H, T, S), nx = axis_tiles(W, T, S);
-    if (ny * nx > INT32_MAX) return false;
-    g.S = S;
-    g.ny = (int)ny;
-    g.nx = (int)nx;
-    return true;
-}
-
-bool rect_ok(const Geo& g, int ty0, int tx0, int nty, int ntx)
-{
-    return ty0 >= 0 && tx0 >= 0 && nty >= 1 && ntx >= 1 && (int64_t)ty0 + nty <= g.ny && (int64_t)tx0 + ntx <= g.nx;
-}
-
-// The first and the last tile along an axis of n tiles that cover pixel p.
-int last_tile(int p, int S, int n) { return p / S < n - 1 ? p / S : n - 1; }
-int first_tile(int p, int S, int O, int n)
-{
-    const int i = last_tile(p, S, n);
-    return i > 0 && p - i * S < O ? i - 1 : i;
+    gather_partials<Sum>(partials, 0, blocks, (int)threadIdx.x, NT, su);
+    block_reduce<Sum>(su, sse);
 }
 
 // The item space of a stitch: row pairs x the frame-aligned eight-column groups that meet [x0, x0 + w).
@@ -560,8 +309,6 @@ bool admissible(int H, int W, int y0, int x0, int h, int w)
     return y0 % 2 == 0 && x0 % 2 == 0 && (h % 2 == 0 || (int64_t)y0 + h == H) && (w % 2 == 0 || (int64_t)x0 + w == W);
 }
 
-bool mult4(int64_t v) { return v % 4 == 0; }
-
 // One plane as the wide path needs it; `back`: elements from the pointer back to the first work item's column 0.
 bool plane_wide(const void* p, int64_t sr, int es, int64_t back)
 {
@@ -576,11 +323,6 @@ bool frame_wide(int fmt, const pc_ft_frame* f, int back)
     return plane_wide(f->u, f->u_row, es, back / 2) && plane_wide(f->v, f->v_row, es, back / 2);
 }
 
-bool f32_wide(const void* p, int64_t ft, int64_t fc, int64_t fh)
-{
-    return reinterpret_cast<uintptr_t>(p) % 16 == 0 && mult4(ft) && mult4(fc) && mult4(fh);
-}
-
 // The one place that decides the access path: the calls launch from it, pc_frame_tiles_plan reports it.
 bool wide_path(int op, int fmt, const pc_ft_frame* frame, const void* f32, int64_t ft, int64_t fc, int64_t fh, int O, int x0,
                const pc_ft_frame* ref)
@@ -591,11 +333,11 @@ bool wide_path(int op, int fmt, const pc_ft_frame* frame, const void* f32, int64
     return (!frame || frame_wide(fmt, frame, back)) && (!ref || frame_wide(fmt, ref, back));
 }
 
+// a frame the call may go without: all zero then
 template <class T>
-Planes<T> planes_of(const pc_ft_frame* f)
+Planes<T> planes_or_none(const pc_ft_frame* f)
 {
-    if (!f) return Planes<T>{nullptr, 0, nullptr, 0, nullptr, 0};
-    return Planes<T>{static_cast<T*>(f->y), f->y_row, static_cast<T*>(f->u), f->u_row, static_cast<T*>(f->v), f->v_row};
+    return f ? planes_of<T>(f) : Planes<T>{nullptr, 0, nullptr, 0, nullptr, 0};
 }
 
 template <class T, bool IL>
@@ -615,8 +357,8 @@ void launch_stitch(bool wide, bool has_ref, dim3 grid, hipStream_t st, const F32
                    const pc_ft_frame* dst, const pc_ft_frame* ref, const Items& it, const Levels& lv, const EmitCoef& k,
                    unsigned long long* part)
 {
-    const Planes<T> d = planes_of<T>(dst);
-    const Planes<const T> r = planes_of<const T>(ref);
+    const Planes<T> d = planes_or_none<T>(dst);
+    const Planes<const T> r = planes_or_none<const T>(ref);
 #define PC_STITCH(WIDE, REF)                                                                                                          \
     hipLaunchKernelGGL((stitch_kernel<T, IL, WIDE, REF>), grid, dim3(NT), 0, st, x, tg, y0, x0, h, w, d, r, it.G, it.items, lv, k, part)
     if (has_ref) {
@@ -641,7 +383,7 @@ extern "C" int pc_frame_tiles_plan(int op, int fmt, const pc_ft_frame* frame, co
     if (x0 < 0 || x0 % 2) return PC_ERR_ARG;
     if (!frame && (op != PC_FT_STITCH || !ref)) return PC_ERR_ARG;
     for (const pc_ft_frame* f : {frame, ref})
-        if (f && (!f->y || !f->u || (!interleaved(fmt) && !f->v))) return PC_ERR_ARG;
+        if (f && !planes_set(fmt, f)) return PC_ERR_ARG;
     *wide = wide_path(op, fmt, frame, f32, ft, fc, fh, O, x0, ref) ? 1 : 0;
     return PC_OK;
 }
@@ -651,9 +393,9 @@ extern "C" int pc_frame_tiles_cut(const pc_ft_frame* src, int fmt, int range, in
 {
     Geo g;
     Levels lv;
-    if (!geo_of(H, W, T, O, g) || !rect_ok(g, ty0, tx0, nty, ntx)) return PC_ERR_ARG;
-    if (!dst || reinterpret_cast<uintptr_t>(dst) % 4 || !frame_ok(fmt, src, W) || !levels_of(fmt, range, lv)) return PC_ERR_ARG;
-    if (upsample != PC_FT_NEAREST && upsample != PC_FT_LINEAR) return PC_ERR_ARG;
+    if (!geo_of(H, W, T, O, INT_MAX, g) || !rect_ok(g, ty0, tx0, nty, ntx)) return PC_ERR_ARG;
+    if (!dst || !aligned(dst, 4) || !frame_ok(fmt, src, W) || !levels_of(fmt, range, lv)) return PC_ERR_ARG;
+    if (!upsample_ok(upsample)) return PC_ERR_ARG;
     const int G8 = T / COLS;
     const int64_t tile_items = (int64_t)T * G8, tiles = (int64_t)nty * ntx;
     if (tile_items > INT32_MAX || tiles > INT32_MAX / 3) return PC_ERR_ARG;
@@ -687,8 +429,8 @@ extern "C" int pc_frame_tiles_stitch(const float* x, int64_t sxt, int64_t sxc, i
     Geo g;
     Items it;
     Levels lv;
-    if (!geo_of(H, W, T, O, g) || !rect_ok(g, ty0, tx0, nty, ntx)) return PC_ERR_ARG;
-    if (!x || reinterpret_cast<uintptr_t>(x) % 4 || sxh < T || sxc < 1 || sxt < 1) return PC_ERR_ARG;
+    if (!geo_of(H, W, T, O, INT_MAX, g) || !rect_ok(g, ty0, tx0, nty, ntx)) return PC_ERR_ARG;
+    if (!x || !aligned(x, 4) || sxh < T || sxc < 1 || sxt < 1) return PC_ERR_ARG;
     if (y0 < 0 || x0 < 0 || h < 1 || w < 1 || (int64_t)y0 + h > H || (int64_t)x0 + w > W || !items_of(x0, h, w, it)) return PC_ERR_ARG;
     if (!admissible(H, W, y0, x0, h, w)) return PC_ERR_ARG;
     // every tile that covers a pixel of the window lies in the rectangle
@@ -699,7 +441,7 @@ extern "C" int pc_frame_tiles_stitch(const float* x, int64_t sxt, int64_t sxc, i
     if (dst && !frame_ok(fmt, dst, w)) return PC_ERR_ARG;
     if (ref) {
         if (!frame_ok(fmt, ref, w)) return PC_ERR_ARG;
-        if (!workspace || reinterpret_cast<uintptr_t>(workspace) % 8 || !sse || reinterpret_cast<uintptr_t>(sse) % 8) return PC_ERR_ARG;
+        if (!workspace || !aligned(workspace, 8) || !sse || !aligned(sse, 8)) return PC_ERR_ARG;
         if (workspace_bytes < (size_t)it.blocks * 3 * sizeof(unsigned long long)) return PC_ERR_ARG;
     }
     const bool wide = wide_path(PC_FT_STITCH, fmt, dst, x, sxt, sxc, sxh, O, x0, ref);

@@ -18,14 +18,13 @@ Everything runs on the current stream of the tensor's device.
 import collections
 import ctypes as C
 import math
-import os
 import struct
 
-from ._lib import ERRORS, PC_OK
+from . import _imagelib
+from ._lib import PC_OK
 from .pixels import Geometry, padding
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_HERE, "libpc_frames.so")
+LIB_PATH = _imagelib.lib_path("frames")
 
 #: every symbol frames_csrc/pc_frames.h declares
 EXPORTS = ["pc_frames_ingest", "pc_frames_emit_workspace_size", "pc_frames_emit", "pc_frames_plan", "pc_frames_strerror",
@@ -37,9 +36,6 @@ UPSAMPLES = {"nearest": 0, "linear": 1}                   # PC_FRAMES_NEAREST, P
 MATRICES = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722), "bt2020": (0.2627, 0.0593)}     # (Kr, Kb); Kg = 1 - Kr - Kb
 INGEST, EMIT = 0, 1                                       # pc_frames_plan's `op`
 
-PC_ERR_HIP = -6                                           # pcodec.h
-
-_lib = None
 _range = range                                            # the functions below take a parameter of that name
 
 
@@ -50,30 +46,24 @@ class Frame(C.Structure):
                 ("v", C.c_void_p), ("v_batch", C.c_int64), ("v_row", C.c_int64)]
 
 
+def _prototypes():
+    i64, vp, ci, cf, fp = C.c_int64, C.c_void_p, C.c_int, C.c_float, C.POINTER(Frame)
+    return {
+        "pc_frames_ingest": (None, [fp, ci, ci, ci, cf, cf, cf, cf, ci, ci, ci, vp, ci, ci, ci, ci, vp]),
+        "pc_frames_emit_workspace_size": (C.c_size_t, [ci, ci, ci]),
+        "pc_frames_emit": (None, [vp, i64, i64, i64, ci, ci, ci, ci, ci, ci, ci, ci, ci, cf, cf, cf, cf, cf, fp, fp, vp, C.c_size_t,
+                                  vp, vp]),
+        "pc_frames_plan": (None, [ci, ci, fp, vp, i64, i64, i64, ci, fp, C.POINTER(ci)]),
+        "pc_frames_strerror": (C.c_char_p, [ci]),
+    }
+
+
 def lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise ImportError(f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                              "(hipcc --offload-arch=gfx950).  progressivecodec_amd has no CPU fallback.")
-        L = C.CDLL(LIB_PATH)
-        i64, vp, ci, cf, fp = C.c_int64, C.c_void_p, C.c_int, C.c_float, C.POINTER(Frame)
-        L.pc_frames_ingest.argtypes = [fp, ci, ci, ci, cf, cf, cf, cf, ci, ci, ci, vp, ci, ci, ci, ci, vp]
-        L.pc_frames_emit_workspace_size.restype = C.c_size_t
-        L.pc_frames_emit_workspace_size.argtypes = [ci, ci, ci]
-        L.pc_frames_emit.argtypes = [vp, i64, i64, i64, ci, ci, ci, ci, ci, ci, ci, ci, ci, cf, cf, cf, cf, cf, fp, fp, vp, C.c_size_t, vp, vp]
-        L.pc_frames_plan.argtypes = [ci, ci, fp, vp, i64, i64, i64, ci, fp, C.POINTER(ci)]
-        L.pc_frames_strerror.restype = C.c_char_p
-        L.pc_frames_strerror.argtypes = [ci]
-        _lib = L
-    return _lib
+    return _imagelib.load(LIB_PATH, _prototypes)
 
 
-class FramesError(RuntimeError):
-    def __init__(self, code, where=""):
-        L = lib()
-        hip = L.pc_frames_last_hip_error() if code == PC_ERR_HIP else 0
-        super().__init__(f"{where}: {ERRORS.get(code, code)} ({L.pc_frames_strerror(code).decode()})" + (f" hipError={hip}" if hip else ""))
+class FramesError(_imagelib.ImageLibError):
+    _lib, _prefix = staticmethod(lib), "pc_frames"
 
 
 def bits_of(fmt):

@@ -3,7 +3,7 @@
  * the per-plane distortion sums out (pc_frames_emit).  DESIGN.md section 13.
  *
  * Kept apart from libpcodec.so and from the other image-side libraries (libpc_pixels.so, libpc_tiles.so, libpc_rate.so): nothing here is
- * part of the codec's numeric contract, byte strings or profiles, and no library of the image domain depends on another.  Plain C, the
+ * part of the codec's numeric contract, byte strings or profiles, and no library of the image domain links another.  Plain C, the
  * conventions of pc_pixels.h: device pointers, int64 strides, status codes PC_OK / PC_ERR_* (pcodec.h), `stream` is a hipStream_t
  * passed as void* (NULL = default stream).  No call allocates device memory or synchronises the host: the caller passes the
  * workspace, and every launch is ordered on `stream`.  Every argument is checked before the first HIP call; a call that returns
@@ -31,24 +31,18 @@
 #define PC_FRAMES_H
 
 #include "pcodec.h"
+#include "pc_yuv_frame.h"
 
 #ifdef __cplusplus
 extern "C" {
 #endif
 
-enum { PC_FRAMES_NV12 = 0, PC_FRAMES_I420 = 1, PC_FRAMES_P010 = 2 };
-enum { PC_FRAMES_LIMITED = 0, PC_FRAMES_FULL = 1 };
-enum { PC_FRAMES_NEAREST = 0, PC_FRAMES_LINEAR = 1 };
+enum { PC_FRAMES_NV12 = PC_YUV_NV12, PC_FRAMES_I420 = PC_YUV_I420, PC_FRAMES_P010 = PC_YUV_P010 };
+enum { PC_FRAMES_LIMITED = PC_YUV_LIMITED, PC_FRAMES_FULL = PC_YUV_FULL };
+enum { PC_FRAMES_NEAREST = PC_YUV_NEAREST, PC_FRAMES_LINEAR = PC_YUV_LINEAR };
 enum { PC_FRAMES_INGEST = 0, PC_FRAMES_EMIT = 1 };
 
-typedef struct pc_frame {
-    void* y;
-    int64_t y_batch, y_row;
-    void* u;                    /* NV12 / P010: the interleaved CbCr plane */
-    int64_t u_batch, u_row;
-    void* v;                    /* I420 only */
-    int64_t v_batch, v_row;
-} pc_frame;
+/* pc_frame: pc_yuv_frame.h, the record every YUV library shares; here all nine members are read */
 
 /* dst[b][0..2][top + r][left + q] = (R, G, B) of luma pixel (r, q), and +0.0f everywhere else.  With C the Cb or Cr plane of codes:
  *   i0 = r >> 1, i1 = i0 + 1 if r is odd else i0 - 1, clamped to [0, Hc-1]; j0, j1 likewise from q;

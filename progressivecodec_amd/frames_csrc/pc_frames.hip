@@ -7,24 +7,20 @@
 // moves at least 32 bits per access (four I420 chroma bytes) and the float planes two 128-bit words.  The access path (WIDE: four
 // elements of a plane and four floats per access; else one by one) only changes the load and store instructions, never which thread
 // handles which sample or in which order it adds: the bits are the same on both.  No LDS on the data path; the sums go thread, wave
-// tree, waves in order (12 words of LDS), then emit_final over the block partials, no atomics.
-#include <hip/hip_runtime.h>
-
-#include <atomic>
-#include <cstdint>
+// tree, waves in order (12 words of LDS), then emit_final over the block partials, no atomics (image_csrc/pc_reduce.h).  The ingest
+// of one item is cut_item of image_csrc/pc_yuv_items.h, as in pc_frame_tiles.hip and pc_clips.hip.
+#include "pc_image_host.h"
+#include "pc_reduce.h"
+#include "pc_tile_grid.h"
+#include "pc_yuv_device.h"
+#include "pc_yuv_items.h"
 
 #include "pc_frames.h"
 
-static std::atomic<int> g_last_hip{0};
-#define HIPCHK(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { g_last_hip = (int)_e; return PC_ERR_HIP; } } while (0)
-
 namespace {
 
-constexpr int NT = 256;                  // threads per block (4 waves)
-constexpr int COLS = 8;                  // luma columns per work item
-
 template <class T>
-struct Planes {                          // pc_frame with typed pointers; strides in elements
+struct BatchPlanes {                     // pc_frame with typed pointers; strides in elements.  Only this library has batches
     T* y;
     int64_t yb, yr;
     T* u;
@@ -33,67 +29,13 @@ struct Planes {                          // pc_frame with typed pointers; stride
     int64_t vb, vr;
 };
 
-struct Levels {
-    int yo, ys, co, cs, maxv;
-};
-
-struct IngestCoef {
-    float a, b, c, d;
-};
-
-struct EmitCoef {
-    float kr, kg, kb, ib, ir;
-};
-
-inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
-
-// four consecutive elements of a plane in one access: a 32-bit word of bytes, a 64-bit word of 16-bit words
-__device__ __forceinline__ void load4(const uint8_t* p, unsigned v[4])
-{
-    const uint32_t w = *reinterpret_cast<const uint32_t*>(p);
-    v[0] = w & 255u; v[1] = (w >> 8) & 255u; v[2] = (w >> 16) & 255u; v[3] = w >> 24;
-}
-
-__device__ __forceinline__ void load4(const uint16_t* p, unsigned v[4])
-{
-    const uint2 w = *reinterpret_cast<const uint2*>(p);
-    v[0] = w.x & 0xffffu; v[1] = w.x >> 16; v[2] = w.y & 0xffffu; v[3] = w.y >> 16;
-}
-
-__device__ __forceinline__ void store4(uint8_t* p, const unsigned v[4])
-{
-    *reinterpret_cast<uint32_t*>(p) = v[0] | (v[1] << 8) | (v[2] << 16) | (v[3] << 24);
-}
-
-__device__ __forceinline__ void store4(uint16_t* p, const unsigned v[4])
-{
-    *reinterpret_cast<uint2*>(p) = make_uint2(v[0] | (v[1] << 16), v[2] | (v[3] << 16));
-}
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
-
-__device__ __forceinline__ float clamp01(float v) { return fminf(fmaxf(v, 0.f), 1.f); }
-
-// One luma pixel of the ingest: its code and the two 16-fold chroma sums -> R, G, B.
-__device__ __forceinline__ void to_rgb(int Y, int cb16, int cr16, const Levels& lv, const IngestCoef& k, float& R, float& G, float& B)
-{
-    const float y = (float)(Y - lv.yo) / (float)lv.ys;
-    const float cb = (float)(cb16 - 16 * lv.co) / (float)(16 * lv.cs);
-    const float cr = (float)(cr16 - 16 * lv.co) / (float)(16 * lv.cs);
-    R = clamp01(y + cr * k.a);
-    G = clamp01((y - cb * k.b) - cr * k.c);
-    B = clamp01(y + cb * k.d);
-}
-
 // Items are the eight-column groups of the PADDED rows: item -> (yp, g), columns 8g .. 8g+7 of row yp of dst.  G = ceil(Wp / 8),
 // items = Hp * G per picture, blocks = ceil(items / NT) per picture.  SH: the bits below the code in an element (P010: 6).
 template <class T, bool IL, bool WIDE>
-__global__ __launch_bounds__(NT) void ingest_kernel(Planes<const T> s, int H, int W, int Hc, int Wc, float* __restrict__ dst, int Hp,
+__global__ __launch_bounds__(NT) void ingest_kernel(BatchPlanes<const T> s, int H, int W, int Hc, int Wc, float* __restrict__ dst, int Hp,
                                                     int Wp, int top, int left, int G, int items, int blocks, int linear, Levels lv,
                                                     IngestCoef k)
 {
-    constexpr int SH = sizeof(T) == 2 ? 6 : 0;
-    constexpr int CS = IL ? 2 : 1;                                // elements from one Cb (Cr) sample to the next
     const int b = blockIdx.x / blocks, blk = blockIdx.x - b * blocks;
     const int item = blk * NT + threadIdx.x;
     if (item >= items) return;
@@ -105,105 +47,20 @@ __global__ __launch_bounds__(NT) void ingest_kernel(Planes<const T> s, int H, in
     for (int c = 0; c < 3; ++c)
 #pragma unroll
         for (int i = 0; i < COLS; ++i) o[c][i] = 0.f;
-    if (y >= 0 && y < H && x0 + COLS - 1 >= 0 && x0 < W) {
-        const int i0 = y >> 1;
-        const int i1 = clampi(i0 + ((y & 1) ? 1 : -1), 0, Hc - 1);
-        const T* yrow = s.y + b * s.yb + (int64_t)y * s.yr;
-        const T* u0 = s.u + b * s.ub + (int64_t)i0 * s.ur;        // Cb of chroma row i0, i1; Cr: one element on, or the V plane
-        const T* u1 = s.u + b * s.ub + (int64_t)i1 * s.ur;
-        const T* v0 = IL ? u0 + 1 : s.v + b * s.vb + (int64_t)i0 * s.vr;
-        const T* v1 = IL ? u1 + 1 : s.v + b * s.vb + (int64_t)i1 * s.vr;
-        if (WIDE && x0 >= 0 && x0 + COLS - 1 < W) {               // x0 is a multiple of 8 here (left is)
-            unsigned Y[COLS];
-            load4(yrow + x0, Y);
-            load4(yrow + x0 + 4, Y + 4);
-            const int jc = x0 >> 1;                                // chroma columns jc .. jc+3 exist; a multiple of 4
-            const int jl = max(jc - 1, 0), jr = min(jc + 4, Wc - 1);
-            unsigned cw[2][2][6];                                  // [row i0, i1][Cb, Cr][columns jl, jc .. jc+3, jr]
-#pragma unroll
-            for (int r = 0; r < 2; ++r) {
-                const T* pu = r ? u1 : u0;
-                const T* pv = r ? v1 : v0;
-                if (r == 1 && !linear) {
-#pragma unroll
-                    for (int j = 0; j < 6; ++j) { cw[1][0][j] = cw[0][0][j]; cw[1][1][j] = cw[0][1][j]; }
-                    break;
-                }
-                if (IL) {
-                    unsigned e[8];
-                    load4(pu + 2 * (int64_t)jc, e);
-                    load4(pu + 2 * (int64_t)jc + 4, e + 4);
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) { cw[r][0][1 + j] = e[2 * j]; cw[r][1][1 + j] = e[2 * j + 1]; }
-                } else {
-                    load4(pu + jc, &cw[r][0][1]);
-                    load4(pv + jc, &cw[r][1][1]);
-                }
-                cw[r][0][0] = pu[CS * (int64_t)jl]; cw[r][1][0] = pv[CS * (int64_t)jl];
-                cw[r][0][5] = pu[CS * (int64_t)jr]; cw[r][1][5] = pv[CS * (int64_t)jr];
-            }
-#pragma unroll
-            for (int i = 0; i < COLS; ++i) {
-                const int j0 = 1 + (i >> 1), j1 = (i & 1) ? j0 + 1 : j0 - 1;
-                int c16[2];
-#pragma unroll
-                for (int p = 0; p < 2; ++p) {
-                    const int c00 = (int)(cw[0][p][j0] >> SH), c01 = (int)(cw[0][p][j1] >> SH);
-                    const int c10 = (int)(cw[1][p][j0] >> SH), c11 = (int)(cw[1][p][j1] >> SH);
-                    c16[p] = linear ? 9 * c00 + 3 * c01 + 3 * c10 + c11 : 16 * c00;
-                }
-                to_rgb((int)(Y[i] >> SH), c16[0], c16[1], lv, k, o[0][i], o[1][i], o[2][i]);
-            }
-        } else {                                                  // element by element; also the items that straddle an edge
-#pragma unroll
-            for (int i = 0; i < COLS; ++i) {
-                const int x = x0 + i;
-                if (x >= 0 && x < W) {
-                    const int64_t j0 = x >> 1;
-                    const int64_t j1 = clampi((int)j0 + ((x & 1) ? 1 : -1), 0, Wc - 1);
-                    int c16[2];
-#pragma unroll
-                    for (int p = 0; p < 2; ++p) {
-                        const T* r0 = p ? v0 : u0;
-                        const T* r1 = p ? v1 : u1;
-                        const int c00 = (int)(r0[CS * j0] >> SH);
-                        if (linear) {
-                            const int c01 = (int)(r0[CS * j1] >> SH), c10 = (int)(r1[CS * j0] >> SH), c11 = (int)(r1[CS * j1] >> SH);
-                            c16[p] = 9 * c00 + 3 * c01 + 3 * c10 + c11;
-                        } else {
-                            c16[p] = 16 * c00;
-                        }
-                    }
-                    to_rgb((int)(yrow[x] >> SH), c16[0], c16[1], lv, k, o[0][i], o[1][i], o[2][i]);
-                }
-            }
-        }
+    if (y >= 0 && y < H && x0 + COLS - 1 >= 0 && x0 < W) {       // x0 is a multiple of 8 on the wide path (left is)
+        const Planes<const T> pic{s.y + b * s.yb, s.yr, s.u + b * s.ub, s.ur, IL ? nullptr : s.v + b * s.vb, s.vr};
+        cut_item<T, IL, WIDE, true>(pic, W, Hc, Wc, y, x0, linear, lv, k, o);
     }
     const int64_t plane = (int64_t)Hp * Wp;
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        float* d = dst + (b * (int64_t)3 + c) * plane + (int64_t)yp * Wp + xp0;
-        if (WIDE) {                                               // Wp is a multiple of 8 here: n == 8
-            *reinterpret_cast<float4*>(d) = make_float4(o[c][0], o[c][1], o[c][2], o[c][3]);
-            *reinterpret_cast<float4*>(d + 4) = make_float4(o[c][4], o[c][5], o[c][6], o[c][7]);
-        } else {
-#pragma unroll
-            for (int i = 0; i < COLS; ++i)
-                if (i < n) d[i] = o[c][i];
-        }
-    }
+    for (int c = 0; c < 3; ++c) store8<WIDE>(dst + (b * (int64_t)3 + c) * plane + (int64_t)yp * Wp + xp0, o[c], n);   // WIDE: Wp is a multiple of 8, n == 8
 }
-
-struct F32 {                             // float planes, strides in elements
-    const float* p;
-    int64_t sb, sc, sh;
-};
 
 // One item of the emit: rows 2i and 2i+1 (`rows` of them exist), luma columns x0 .. x0+n-1, chroma row i, columns x0/2 ...  FULL: n == 8
 // and every access is wide; else element by element.  The whole item is compiled twice, not only its loads and stores, so that the
 // two kinds of access never meet in one basic block (where the compiler merges them into the narrow kind).
 template <class T, bool IL, bool FULL, bool HAS_REF>
-__device__ __forceinline__ void emit_item(const F32& x, int top, int left, int H, const Planes<T>& dst, const Planes<const T>& ref, int b,
+__device__ __forceinline__ void emit_item(const F32& x, int top, int left, int H, const BatchPlanes<T>& dst, const BatchPlanes<const T>& ref, int b,
                                           int i, int x0, int n, const Levels& lv, const EmitCoef& k, unsigned long long su[3])
 {
     constexpr int SH = sizeof(T) == 2 ? 6 : 0;
@@ -218,7 +75,7 @@ __device__ __forceinline__ void emit_item(const F32& x, int top, int left, int H
         float c[3][COLS];
 #pragma unroll
         for (int ch = 0; ch < 3; ++ch) {
-            const float* s = x.p + b * x.sb + ch * x.sc + (int64_t)(top + yy) * x.sh + left + x0;
+            const float* s = x.p + b * x.st + ch * x.sc + (int64_t)(top + yy) * x.sh + left + x0;
             if (FULL) {
                 const float4 f0 = *reinterpret_cast<const float4*>(s), f1 = *reinterpret_cast<const float4*>(s + 4);
                 c[ch][0] = f0.x; c[ch][1] = f0.y; c[ch][2] = f0.z; c[ch][3] = f0.w;
@@ -229,21 +86,12 @@ __device__ __forceinline__ void emit_item(const F32& x, int top, int left, int H
             }
         }
 #pragma unroll
-        for (int q = 0; q < COLS; ++q) {
-            const float R = clamp01(c[0][q]), Gc = clamp01(c[1][q]), Bc = clamp01(c[2][q]);
-            const float Yf = (k.kr * R + k.kg * Gc) + k.kb * Bc;
-            const float Cb = (Bc - Yf) * k.ib, Cr = (R - Yf) * k.ir;
-            yq[r][q] = (unsigned)clampi((int)rintf(Yf * (float)lv.ys + (float)lv.yo), 0, lv.maxv);
-            ub[r][q] = Cb * (float)lv.cs;
-            ur[r][q] = Cr * (float)lv.cs;
-        }
+        for (int q = 0; q < COLS; ++q) emit_px(c[0][q], c[1][q], c[2][q], lv, k, yq[r][q], ub[r][q], ur[r][q]);
     }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-        const float mb = ((ub[0][2 * j] + ub[0][2 * j + 1]) + (ub[1][2 * j] + ub[1][2 * j + 1])) * 0.25f + (float)lv.co;
-        const float mr = ((ur[0][2 * j] + ur[0][2 * j + 1]) + (ur[1][2 * j] + ur[1][2 * j + 1])) * 0.25f + (float)lv.co;
-        cq[0][j] = (unsigned)clampi((int)rintf(mb), 0, lv.maxv);
-        cq[1][j] = (unsigned)clampi((int)rintf(mr), 0, lv.maxv);
+        cq[0][j] = (unsigned)emit_chroma(ub[0][2 * j], ub[0][2 * j + 1], ub[1][2 * j], ub[1][2 * j + 1], lv);
+        cq[1][j] = (unsigned)emit_chroma(ur[0][2 * j], ur[0][2 * j + 1], ur[1][2 * j], ur[1][2 * j + 1], lv);
     }
     if (dst.y) {
 #pragma unroll
@@ -342,11 +190,10 @@ __device__ __forceinline__ void emit_item(const F32& x, int top, int left, int H
 // Items are the eight-column groups of the WINDOW's row pairs: item -> (i, g), rows 2i and 2i+1, columns 8g .. 8g+7 of the picture,
 // chroma row i, columns 4g .. 4g+3.  G = ceil(W / 8), items = Hc * G per picture.  partials: [gridDim.x][3].
 template <class T, bool IL, bool WIDE, bool HAS_REF>
-__global__ __launch_bounds__(NT) void emit_kernel(F32 x, int top, int left, int H, int W, Planes<T> dst, Planes<const T> ref, int G,
+__global__ __launch_bounds__(NT) void emit_kernel(F32 x, int top, int left, int H, int W, BatchPlanes<T> dst, BatchPlanes<const T> ref, int G,
                                                   int items, int blocks, Levels lv, EmitCoef k,
                                                   unsigned long long* __restrict__ partials)
 {
-    __shared__ unsigned long long red[NT / 64][3];
     const int b = blockIdx.x / blocks, blk = blockIdx.x - b * blocks;
     const int item = blk * NT + threadIdx.x;
     unsigned long long su[3] = {0ull, 0ull, 0ull};
@@ -356,87 +203,44 @@ __global__ __launch_bounds__(NT) void emit_kernel(F32 x, int top, int left, int 
         if (WIDE && n == COLS) emit_item<T, IL, true, HAS_REF>(x, top, left, H, dst, ref, b, i, x0, n, lv, k, su);
         else emit_item<T, IL, false, HAS_REF>(x, top, left, H, dst, ref, b, i, x0, n, lv, k, su);
     }
-    if (HAS_REF) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1)
-#pragma unroll
-            for (int p = 0; p < 3; ++p) su[p] += __shfl_down(su[p], off, 64);
-        if ((threadIdx.x & 63) == 0)
-#pragma unroll
-            for (int p = 0; p < 3; ++p) red[threadIdx.x >> 6][p] = su[p];
-        __syncthreads();
-        if (threadIdx.x < 3) {
-            unsigned long long a = red[0][threadIdx.x];
-            for (int wv = 1; wv < NT / 64; ++wv) a += red[wv][threadIdx.x];
-            partials[(int64_t)blockIdx.x * 3 + threadIdx.x] = a;
-        }
-    }
+    if (HAS_REF) block_reduce<Sum>(su, partials + (int64_t)blockIdx.x * 3);
 }
 
 // One block per picture: its block partials (thread t takes t, t + NT, ...; wave tree; waves in order).
 __global__ __launch_bounds__(NT) void emit_final_kernel(const unsigned long long* __restrict__ partials, int blocks,
                                                         unsigned long long* __restrict__ sse)
 {
-    __shared__ unsigned long long red[NT / 64][3];
     const int b = blockIdx.x;
-    const unsigned long long* p = partials + (int64_t)b * blocks * 3;
     unsigned long long su[3] = {0ull, 0ull, 0ull};
-    for (int t = threadIdx.x; t < blocks; t += NT)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) su[c] += p[(int64_t)t * 3 + c];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) su[c] += __shfl_down(su[c], off, 64);
-    if ((threadIdx.x & 63) == 0)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) red[threadIdx.x >> 6][c] = su[c];
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        unsigned long long a = red[0][threadIdx.x];
-        for (int wv = 1; wv < NT / 64; ++wv) a += red[wv][threadIdx.x];
-        sse[b * 3 + threadIdx.x] = a;
-    }
-}
-
-bool fmt_ok(int fmt) { return fmt == PC_FRAMES_NV12 || fmt == PC_FRAMES_I420 || fmt == PC_FRAMES_P010; }
-bool interleaved(int fmt) { return fmt != PC_FRAMES_I420; }
-int elem_bytes(int fmt) { return fmt == PC_FRAMES_P010 ? 2 : 1; }
-
-bool levels_of(int fmt, int range, Levels& lv)
-{
-    const int n = fmt == PC_FRAMES_P010 ? 10 : 8, s = 1 << (n - 8), maxv = (1 << n) - 1;
-    if (range == PC_FRAMES_LIMITED) lv = Levels{16 * s, 219 * s, 128 * s, 224 * s, maxv};
-    else if (range == PC_FRAMES_FULL) lv = Levels{0, maxv, 128 * s, maxv, maxv};
-    else return false;
-    return true;
+    gather_partials<Sum>(partials + (int64_t)b * blocks * 3, 0, blocks, (int)threadIdx.x, NT, su);
+    block_reduce<Sum>(su, sse + b * 3);
 }
 
 // One plane of B pictures of `rows` rows of `len` elements: pointer aligned to its element, strides in range; `disjoint`
 // (destinations): rows inside pictures, which is sufficient (not necessary) for no element of the plane to be written twice.
-bool plane_ok(const void* p, int64_t sb, int64_t sr, int es, int B, int rows, int64_t len, bool disjoint)
+bool batch_plane_ok(const void* p, int64_t sb, int64_t sr, int es, int B, int rows, int64_t len, bool disjoint)
 {
     if (!p || reinterpret_cast<uintptr_t>(p) % es || sr < len || sb < 1) return false;
     if (disjoint && B > 1 && sb < (int64_t)(rows - 1) * sr + len) return false;
     return true;
 }
 
-bool frame_ok(int fmt, const pc_frame* f, int B, int H, int W, bool disjoint)
+bool batch_frame_ok(int fmt, const pc_frame* f, int B, int H, int W, bool disjoint)
 {
     if (!f || !fmt_ok(fmt)) return false;
     const int es = elem_bytes(fmt), Hc = (int)cdiv(H, 2);
     const int64_t Wc = cdiv(W, 2);
-    if (!plane_ok(f->y, f->y_batch, f->y_row, es, B, H, W, disjoint)) return false;
-    if (interleaved(fmt)) return plane_ok(f->u, f->u_batch, f->u_row, es, B, Hc, 2 * Wc, disjoint);
-    return plane_ok(f->u, f->u_batch, f->u_row, es, B, Hc, Wc, disjoint) && plane_ok(f->v, f->v_batch, f->v_row, es, B, Hc, Wc, disjoint);
+    if (!batch_plane_ok(f->y, f->y_batch, f->y_row, es, B, H, W, disjoint)) return false;
+    if (interleaved(fmt)) return batch_plane_ok(f->u, f->u_batch, f->u_row, es, B, Hc, 2 * Wc, disjoint);
+    return batch_plane_ok(f->u, f->u_batch, f->u_row, es, B, Hc, Wc, disjoint) && batch_plane_ok(f->v, f->v_batch, f->v_row, es, B, Hc, Wc, disjoint);
 }
 
 // Sizes every call shares: B, rows, cols >= 1 and the block count of an item space of rows x ceil(cols / 8) per picture in 32 bits.
-struct Grid {
+struct Items {
     int G, items, blocks;
 };
 
-bool grid_of(int B, int rows, int cols, Grid& g)
+bool items_of(int B, int rows, int cols, Items& g)
 {
     if (B < 1 || rows < 1 || cols < 1) return false;
     const int64_t G = cdiv(cols, COLS), items = (int64_t)rows * G;
@@ -449,10 +253,8 @@ bool grid_of(int B, int rows, int cols, Grid& g)
     return true;
 }
 
-bool mult4(int64_t v) { return v % 4 == 0; }
-
 // The alignment of a frame as the wide path needs it: every plane pointer on four elements, every stride a multiple of 4.
-bool frame_wide(int fmt, const pc_frame* f)
+bool batch_frame_wide(int fmt, const pc_frame* f)
 {
     const uintptr_t a = 4 * (uintptr_t)elem_bytes(fmt);
     if (reinterpret_cast<uintptr_t>(f->y) % a || !mult4(f->y_batch) || !mult4(f->y_row)) return false;
@@ -465,9 +267,9 @@ bool frame_wide(int fmt, const pc_frame* f)
 bool wide_path(int op, int fmt, const pc_frame* frame, const void* f32, int64_t fb, int64_t fc, int64_t fh, int left,
                const pc_frame* ref)
 {
-    if (reinterpret_cast<uintptr_t>(f32) % 16 || !mult4(fb) || !mult4(fc) || !mult4(fh)) return false;
-    if (op == PC_FRAMES_INGEST) return fh % 8 == 0 && left % 8 == 0 && frame_wide(fmt, frame);     // fh = Wp: no partial last item
-    return left % 4 == 0 && (!frame || frame_wide(fmt, frame)) && (!ref || frame_wide(fmt, ref));
+    if (!f32_wide(f32, fb, fc, fh)) return false;
+    if (op == PC_FRAMES_INGEST) return fh % 8 == 0 && left % 8 == 0 && batch_frame_wide(fmt, frame);     // fh = Wp: no partial last item
+    return left % 4 == 0 && (!frame || batch_frame_wide(fmt, frame)) && (!ref || batch_frame_wide(fmt, ref));
 }
 
 bool window_ok(int B, int H, int W, int Hp, int Wp, int top, int left)
@@ -477,18 +279,18 @@ bool window_ok(int B, int H, int W, int Hp, int Wp, int top, int left)
 }
 
 template <class T>
-Planes<T> planes_of(const pc_frame* f)
+BatchPlanes<T> batch_planes_of(const pc_frame* f)
 {
-    if (!f) return Planes<T>{nullptr, 0, 0, nullptr, 0, 0, nullptr, 0, 0};
-    return Planes<T>{static_cast<T*>(f->y), f->y_batch, f->y_row, static_cast<T*>(f->u), f->u_batch, f->u_row, static_cast<T*>(f->v),
-                     f->v_batch, f->v_row};
+    if (!f) return BatchPlanes<T>{nullptr, 0, 0, nullptr, 0, 0, nullptr, 0, 0};
+    return BatchPlanes<T>{static_cast<T*>(f->y), f->y_batch, f->y_row, static_cast<T*>(f->u), f->u_batch, f->u_row, static_cast<T*>(f->v),
+                          f->v_batch, f->v_row};
 }
 
 template <class T, bool IL>
 void launch_ingest(bool wide, dim3 grid, hipStream_t st, const pc_frame* src, int H, int W, float* dst, int Hp, int Wp, int top, int left,
-                   const Grid& g, int linear, const Levels& lv, const IngestCoef& k)
+                   const Items& g, int linear, const Levels& lv, const IngestCoef& k)
 {
-    const Planes<const T> s = planes_of<const T>(src);
+    const BatchPlanes<const T> s = batch_planes_of<const T>(src);
     const int Hc = (H + 1) / 2, Wc = (W + 1) / 2;
     if (wide)
         hipLaunchKernelGGL((ingest_kernel<T, IL, true>), grid, dim3(NT), 0, st, s, H, W, Hc, Wc, dst, Hp, Wp, top, left, g.G, g.items,
@@ -500,10 +302,10 @@ void launch_ingest(bool wide, dim3 grid, hipStream_t st, const pc_frame* src, in
 
 template <class T, bool IL>
 void launch_emit(bool wide, bool has_ref, dim3 grid, hipStream_t st, const F32& x, int top, int left, int H, int W, const pc_frame* dst,
-                 const pc_frame* ref, const Grid& g, const Levels& lv, const EmitCoef& k, unsigned long long* part)
+                 const pc_frame* ref, const Items& g, const Levels& lv, const EmitCoef& k, unsigned long long* part)
 {
-    const Planes<T> d = planes_of<T>(dst);
-    const Planes<const T> r = planes_of<const T>(ref);
+    const BatchPlanes<T> d = batch_planes_of<T>(dst);
+    const BatchPlanes<const T> r = batch_planes_of<const T>(ref);
 #define PC_EMIT(WIDE, REF)                                                                                                            \
     hipLaunchKernelGGL((emit_kernel<T, IL, WIDE, REF>), grid, dim3(NT), 0, st, x, top, left, H, W, d, r, g.G, g.items, g.blocks, lv, k, \
                        part)
@@ -524,7 +326,7 @@ extern "C" int pc_frames_plan(int op, int fmt, const pc_frame* frame, const void
     if (op == PC_FRAMES_INGEST) ref = nullptr;
     if (!frame && (op != PC_FRAMES_EMIT || !ref)) return PC_ERR_ARG;
     for (const pc_frame* f : {frame, ref})
-        if (f && (!f->y || !f->u || (!interleaved(fmt) && !f->v))) return PC_ERR_ARG;
+        if (f && !planes_set(fmt, f)) return PC_ERR_ARG;
     *wide = wide_path(op, fmt, frame, f32, fb, fc, fh, left, ref) ? 1 : 0;
     return PC_OK;
 }
@@ -532,12 +334,12 @@ extern "C" int pc_frames_plan(int op, int fmt, const pc_frame* frame, const void
 extern "C" int pc_frames_ingest(const pc_frame* src, int fmt, int range, int upsample, float a, float b, float c, float d, int B, int H,
                                 int W, float* dst, int Hp, int Wp, int top, int left, void* stream)
 {
-    Grid g;
+    Items g;
     Levels lv;
-    if (!dst || reinterpret_cast<uintptr_t>(dst) % 4 || !window_ok(B, H, W, Hp, Wp, top, left)) return PC_ERR_ARG;
-    if (!frame_ok(fmt, src, B, H, W, false) || !levels_of(fmt, range, lv)) return PC_ERR_ARG;
-    if (upsample != PC_FRAMES_NEAREST && upsample != PC_FRAMES_LINEAR) return PC_ERR_ARG;
-    if (!grid_of(B, Hp, Wp, g)) return PC_ERR_ARG;
+    if (!dst || !aligned(dst, 4) || !window_ok(B, H, W, Hp, Wp, top, left)) return PC_ERR_ARG;
+    if (!batch_frame_ok(fmt, src, B, H, W, false) || !levels_of(fmt, range, lv)) return PC_ERR_ARG;
+    if (!upsample_ok(upsample)) return PC_ERR_ARG;
+    if (!items_of(B, Hp, Wp, g)) return PC_ERR_ARG;
     const int64_t plane = (int64_t)Hp * Wp;
     const bool wide = wide_path(PC_FRAMES_INGEST, fmt, src, dst, 3 * plane, plane, Wp, left, nullptr);
     const IngestCoef k{a, b, c, d};
@@ -553,24 +355,24 @@ extern "C" int pc_frames_ingest(const pc_frame* src, int fmt, int range, int ups
 
 extern "C" size_t pc_frames_emit_workspace_size(int B, int H, int W)
 {
-    Grid g;
-    return H >= 1 && grid_of(B, (int)cdiv(H, 2), W, g) ? (size_t)B * g.blocks * 3 * sizeof(unsigned long long) : 0;
+    Items g;
+    return H >= 1 && items_of(B, (int)cdiv(H, 2), W, g) ? (size_t)B * g.blocks * 3 * sizeof(unsigned long long) : 0;
 }
 
 extern "C" int pc_frames_emit(const float* x, int64_t sxb, int64_t sxc, int64_t sxh, int Hp, int Wp, int top, int left, int B, int H,
                               int W, int fmt, int range, float kr, float kg, float kb, float ib, float ir, const pc_frame* dst,
                               const pc_frame* ref, void* workspace, size_t workspace_bytes, uint64_t* sse, void* stream)
 {
-    Grid g;
+    Items g;
     Levels lv;
-    if (!x || reinterpret_cast<uintptr_t>(x) % 4 || !window_ok(B, H, W, Hp, Wp, top, left)) return PC_ERR_ARG;
+    if (!x || !aligned(x, 4) || !window_ok(B, H, W, Hp, Wp, top, left)) return PC_ERR_ARG;
     if (sxh < Wp || sxc < 1 || sxb < 1 || !fmt_ok(fmt) || !levels_of(fmt, range, lv)) return PC_ERR_ARG;
     if (!dst && !ref) return PC_ERR_ARG;
-    if (dst && !frame_ok(fmt, dst, B, H, W, true)) return PC_ERR_ARG;
-    if (ref && !frame_ok(fmt, ref, B, H, W, false)) return PC_ERR_ARG;
-    if (!grid_of(B, (int)cdiv(H, 2), W, g)) return PC_ERR_ARG;
+    if (dst && !batch_frame_ok(fmt, dst, B, H, W, true)) return PC_ERR_ARG;
+    if (ref && !batch_frame_ok(fmt, ref, B, H, W, false)) return PC_ERR_ARG;
+    if (!items_of(B, (int)cdiv(H, 2), W, g)) return PC_ERR_ARG;
     if (ref) {
-        if (!workspace || reinterpret_cast<uintptr_t>(workspace) % 8 || !sse || reinterpret_cast<uintptr_t>(sse) % 8) return PC_ERR_ARG;
+        if (!workspace || !aligned(workspace, 8) || !sse || !aligned(sse, 8)) return PC_ERR_ARG;
         if (workspace_bytes < (size_t)B * g.blocks * 3 * sizeof(unsigned long long)) return PC_ERR_ARG;
     }
     const bool wide = wide_path(PC_FRAMES_EMIT, fmt, dst, x, sxb, sxc, sxh, left, ref);

@@ -6,12 +6,11 @@ inputs and 5-D inputs raise; `ssim()` requires H, W >= win_size (the library wou
 `ms_ssim()` takes 2 to 5 weights.  There is no CPU fallback: CPU tensors raise before any device call.
 """
 import ctypes as C
-import os
 
-from ._lib import ERRORS, PC_OK
+from . import _imagelib
+from ._lib import PC_OK
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_HERE, "libpc_metrics.so")
+LIB_PATH = _imagelib.lib_path("metrics")
 
 #: every symbol metrics_csrc/pc_metrics.h declares
 EXPORTS = ["pc_msssim_workspace_size", "pc_msssim", "pc_msssim_plan", "pc_metrics_strerror", "pc_metrics_last_hip_error"]
@@ -19,34 +18,25 @@ EXPORTS = ["pc_msssim_workspace_size", "pc_msssim", "pc_msssim_plan", "pc_metric
 #: the library's default scale weights (Wang, Simoncelli, Bovik 2003)
 MS_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)
 
-_lib = None
+
+def _prototypes():
+    i64, vp = C.c_int64, C.c_void_p
+    return {
+        "pc_msssim_workspace_size": (C.c_size_t, [C.c_int] * 6),
+        "pc_msssim": (None, [vp, i64, i64, i64, vp, i64, i64, i64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float,
+                             C.c_float, C.c_float, C.c_int, C.POINTER(C.c_float), C.c_int, vp, C.c_size_t, vp, vp, vp]),
+        "pc_msssim_plan": (None, [vp, i64, i64, i64, vp, i64, i64, i64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp,
+                                  C.POINTER(C.c_int)]),
+        "pc_metrics_strerror": (C.c_char_p, [C.c_int]),
+    }
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise ImportError(f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                              "(hipcc --offload-arch=gfx950).  progressivecodec_amd has no CPU fallback.")
-        L = C.CDLL(LIB_PATH)
-        i64, vp = C.c_int64, C.c_void_p
-        L.pc_msssim_workspace_size.restype = C.c_size_t
-        L.pc_msssim_workspace_size.argtypes = [C.c_int] * 6
-        L.pc_msssim.argtypes = [vp, i64, i64, i64, vp, i64, i64, i64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float,
-                                C.c_float, C.c_float, C.c_int, C.POINTER(C.c_float), C.c_int, vp, C.c_size_t, vp, vp, vp]
-        L.pc_msssim_plan.argtypes = [vp, i64, i64, i64, vp, i64, i64, i64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp,
-                                     C.POINTER(C.c_int)]
-        L.pc_metrics_strerror.restype = C.c_char_p
-        L.pc_metrics_strerror.argtypes = [C.c_int]
-        _lib = L
-    return _lib
+    return _imagelib.load(LIB_PATH, _prototypes)
 
 
-class MetricsError(RuntimeError):
-    def __init__(self, code, where=""):
-        L = lib()
-        hip = L.pc_metrics_last_hip_error() if code == -6 else 0
-        super().__init__(f"{where}: {ERRORS.get(code, code)} ({L.pc_metrics_strerror(code).decode()})" + (f" hipError={hip}" if hip else ""))
+class MetricsError(_imagelib.ImageLibError):
+    _lib, _prefix = staticmethod(lib), "pc_metrics"
 
 
 def _check_inputs(X, Y, win, win_size):

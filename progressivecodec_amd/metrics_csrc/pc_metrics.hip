@@ -4,16 +4,11 @@
 // go to a slab [s][plane][tile]), then, except after the last scale, one pool2x2 launch into the workspace.  One msssim_final launch
 // reduces the slabs per image.  Every sum runs in a fixed order (no atomics), and no block reads two planes, so a value is bitwise
 // reproducible and independent of the image's batch neighbours.
-#include <hip/hip_runtime.h>
-
-#include <atomic>
 #include <cmath>
-#include <cstdint>
+
+#include "pc_image_host.h"
 
 #include "pc_metrics.h"
-
-static std::atomic<int> g_last_hip{0};
-#define HIPCHK(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { g_last_hip = (int)_e; return PC_ERR_HIP; } } while (0)
 
 namespace {
 
@@ -36,7 +31,6 @@ struct FinalArgs {
     double w[MAX_LEVELS];
 };
 
-inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 inline int64_t align256(int64_t n) { return (n + 255) / 256 * 256; }
 
 // Staged plane tile: (TH + WS - 1) rows of SX floats (16-byte rows for float4 stores); the H pass output: five moments of TH rows of

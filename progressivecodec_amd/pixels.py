@@ -14,13 +14,12 @@ raise ValueError before any device call.  Everything runs on the current stream 
 import collections
 import ctypes as C
 import math
-import os
 
-from ._lib import ERRORS, PC_OK
+from . import _imagelib
+from ._lib import PC_OK
 from .harness import compute_padding
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_HERE, "libpc_pixels.so")
+LIB_PATH = _imagelib.lib_path("pixels")
 
 #: every symbol pixels_csrc/pc_pixels.h declares
 EXPORTS = ["pc_pixels_ingest_u8", "pc_pixels_emit_workspace_size", "pc_pixels_emit_u8", "pc_pixels_plan", "pc_pixels_strerror",
@@ -30,36 +29,25 @@ LAYOUTS = {"hwc": 0, "chw": 1}            # PC_PIXELS_HWC, PC_PIXELS_CHW
 ROUNDINGS = {"nearest": 0, "trunc": 1}    # PC_PIXELS_NEAREST (rintf, half to even), PC_PIXELS_TRUNC (mul(255).byte())
 INGEST, EMIT = 0, 1                       # pc_pixels_plan's `op`
 
-PC_ERR_HIP = -6                           # pcodec.h
 
-_lib = None
+def _prototypes():
+    i64, vp, ci = C.c_int64, C.c_void_p, C.c_int
+    u8v = [vp, ci, i64, i64, i64]                                   # a u8 view: pointer, layout, batch / plane / row stride in bytes
+    return {
+        "pc_pixels_ingest_u8": (None, u8v + [ci, ci, ci, vp, ci, ci, ci, ci, vp]),
+        "pc_pixels_emit_workspace_size": (C.c_size_t, [ci, ci, ci]),
+        "pc_pixels_emit_u8": (None, [vp, i64, i64, i64, ci, ci, ci, ci, ci, ci, ci, ci] + u8v + u8v + [vp, C.c_size_t, vp, vp, vp]),
+        "pc_pixels_plan": (None, [ci] + u8v + [vp, i64, i64, i64, ci, ci, ci, ci, ci] + u8v + [C.POINTER(ci)]),
+        "pc_pixels_strerror": (C.c_char_p, [ci]),
+    }
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise ImportError(f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                              "(hipcc --offload-arch=gfx950).  progressivecodec_amd has no CPU fallback.")
-        L = C.CDLL(LIB_PATH)
-        i64, vp, ci = C.c_int64, C.c_void_p, C.c_int
-        u8v = [vp, ci, i64, i64, i64]                                   # a u8 view: pointer, layout, batch / plane / row stride in bytes
-        L.pc_pixels_ingest_u8.argtypes = u8v + [ci, ci, ci, vp, ci, ci, ci, ci, vp]
-        L.pc_pixels_emit_workspace_size.restype = C.c_size_t
-        L.pc_pixels_emit_workspace_size.argtypes = [ci, ci, ci]
-        L.pc_pixels_emit_u8.argtypes = [vp, i64, i64, i64, ci, ci, ci, ci, ci, ci, ci, ci] + u8v + u8v + [vp, C.c_size_t, vp, vp, vp]
-        L.pc_pixels_plan.argtypes = [ci] + u8v + [vp, i64, i64, i64, ci, ci, ci, ci, ci] + u8v + [C.POINTER(ci)]
-        L.pc_pixels_strerror.restype = C.c_char_p
-        L.pc_pixels_strerror.argtypes = [ci]
-        _lib = L
-    return _lib
+    return _imagelib.load(LIB_PATH, _prototypes)
 
 
-class PixelsError(RuntimeError):
-    def __init__(self, code, where=""):
-        L = lib()
-        hip = L.pc_pixels_last_hip_error() if code == PC_ERR_HIP else 0
-        super().__init__(f"{where}: {ERRORS.get(code, code)} ({L.pc_pixels_strerror(code).decode()})" + (f" hipError={hip}" if hip else ""))
+class PixelsError(_imagelib.ImageLibError):
+    _lib, _prefix = staticmethod(lib), "pc_pixels"
 
 
 class Geometry(collections.namedtuple("Geometry", "H W Hp Wp top left")):

@@ -5,15 +5,9 @@
 // image.  The access path (WIDE: a 32-bit word of bytes, a 128-bit word of floats; else byte by byte and float by float) only changes
 // the load and store instructions, never which thread handles which pixel or in which order it adds: the bits are the same on both.
 // The distortion sums run in a fixed order (thread, wave tree, waves in order, then emit_final over the block partials), no atomics.
-#include <hip/hip_runtime.h>
-
-#include <atomic>
-#include <cstdint>
+#include "pc_image_host.h"
 
 #include "pc_pixels.h"
-
-static std::atomic<int> g_last_hip{0};
-#define HIPCHK(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { g_last_hip = (int)_e; return PC_ERR_HIP; } } while (0)
 
 namespace {
 
@@ -41,8 +35,6 @@ struct Partial {                         // one block's sums per channel
     double f[3];
     unsigned long long u[3];
 };
-
-inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 // The 12 bytes of pixels x0 .. x0+3 of row y of image b: v[c][i].  n < 4: only pixels 0 .. n-1 exist (the others read as 0).
 template <bool WIDE>
@@ -350,8 +342,6 @@ bool grid_of(int B, int rows, int cols, Grid& g)
     return true;
 }
 
-bool mult4(int64_t v) { return v % 4 == 0; }
-
 // The alignment of a u8 view as the wide path needs it; `shift`: bytes from the pointer back to the first work item's column 0.
 bool u8_wide(const void* p, int layout, int64_t sb, int64_t sp, int64_t sr, int64_t shift)
 {
@@ -361,7 +351,7 @@ bool u8_wide(const void* p, int layout, int64_t sb, int64_t sp, int64_t sr, int6
 
 bool f32_wide(const void* p, int64_t fb, int64_t fc, int64_t fh, int64_t shift)
 {
-    return reinterpret_cast<uintptr_t>(p) % 16 == 0 && mult4(fb) && mult4(fc) && mult4(fh) && mult4(shift);
+    return aligned(p, 16) && mult4(fb) && mult4(fc) && mult4(fh) && mult4(shift);
 }
 
 // The one place that decides the access path: the calls launch from it, pc_pixels_plan reports it.
@@ -377,7 +367,7 @@ bool wide_path(int op, const void* u8, int layout, int64_t sb, int64_t sp, int64
 bool ingest_args_ok(const void* src, int layout, int64_t sb, int64_t sp, int64_t sr, int B, int H, int W, const void* dst, int Hp,
                     int Wp, int top, int left, Grid& g)
 {
-    if (!dst || reinterpret_cast<uintptr_t>(dst) % 4 || B < 1 || H < 1 || W < 1) return false;
+    if (!dst || !aligned(dst, 4) || B < 1 || H < 1 || W < 1) return false;
     if (top < 0 || left < 0 || Hp < 1 || Wp < 1 || (int64_t)top + H > Hp || (int64_t)left + W > Wp) return false;
     return view_ok(src, layout, sb, sp, sr, B, H, W, false) && grid_of(B, Hp, Wp, g);
 }
@@ -386,7 +376,7 @@ bool emit_args_ok(const void* x, int64_t sxb, int64_t sxc, int64_t sxh, int Hp, 
                   const void* dst, int dst_layout, int64_t db, int64_t dp, int64_t dr, const void* ref, int ref_layout, int64_t rb,
                   int64_t rp, int64_t rr, Grid& g)
 {
-    if (!x || reinterpret_cast<uintptr_t>(x) % 4 || B < 1 || H < 1 || W < 1) return false;
+    if (!x || !aligned(x, 4) || B < 1 || H < 1 || W < 1) return false;
     if (top < 0 || left < 0 || Hp < 1 || Wp < 1 || (int64_t)top + H > Hp || (int64_t)left + W > Wp) return false;
     if (sxh < Wp || sxc < 1 || sxb < 1) return false;
     if (dst ? !view_ok(dst, dst_layout, db, dp, dr, B, H, W, true) : !ref) return false;        // sums only: no image is written
@@ -445,8 +435,8 @@ extern "C" int pc_pixels_emit_u8(const float* x, int64_t sxb, int64_t sxc, int64
         return PC_ERR_ARG;
     if (rounding != PC_PIXELS_NEAREST && rounding != PC_PIXELS_TRUNC) return PC_ERR_ARG;
     if (ref) {
-        if (!workspace || reinterpret_cast<uintptr_t>(workspace) % 8) return PC_ERR_ARG;
-        if (!sse_u8 || reinterpret_cast<uintptr_t>(sse_u8) % 8 || !sse_f || reinterpret_cast<uintptr_t>(sse_f) % 8) return PC_ERR_ARG;
+        if (!workspace || !aligned(workspace, 8)) return PC_ERR_ARG;
+        if (!sse_u8 || !aligned(sse_u8, 8) || !sse_f || !aligned(sse_f, 8)) return PC_ERR_ARG;
         if (workspace_bytes < (size_t)B * g.blocks * sizeof(Partial)) return PC_ERR_ARG;
     }
     const bool wide = wide_path(PC_PIXELS_EMIT, dst, dst_layout, d_batch, d_plane, d_row, x, sxb, sxc, sxh, left, ref, ref_layout,

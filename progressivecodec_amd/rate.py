@@ -20,49 +20,38 @@ control inside compress_with_ac, REM models and WACNN, a level-major layout, unt
 """
 import collections
 import ctypes as C
-import os
 from fractions import Fraction
 
-from ._lib import ERRORS, PC_OK
+from . import _imagelib
+from ._lib import PC_OK
 from .pixels import ROUNDINGS
 from .tiles import HEADER_BYTES, TileGrid, _check_tiles, _view3, grid_of, pack_tiled
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_HERE, "libpc_rate.so")
+LIB_PATH = _imagelib.lib_path("rate")
 
 #: every symbol rate_csrc/pc_rate.h declares
 EXPORTS = ["pc_rate_workspace_size", "pc_rate_tile_sse_u8", "pc_rate_plan", "pc_rate_strerror", "pc_rate_last_hip_error"]
 
-PC_ERR_HIP = -6                           # pcodec.h
 TABLE_ENTRY_BYTES = 16                    # a tile's (offset, length) in the PCT1 / PCT2 table
 
-_lib = None
+
+def _prototypes():
+    i64, vp, ci = C.c_int64, C.c_void_p, C.c_int
+    u8v = [vp, ci, i64, i64]                                        # a u8 view: pointer, layout, plane / row stride in bytes
+    return {
+        "pc_rate_workspace_size": (C.c_size_t, [ci, ci]),
+        "pc_rate_tile_sse_u8": (None, [vp, i64, i64, i64] + [ci] * 7 + u8v + [vp, C.c_size_t, vp, vp]),
+        "pc_rate_plan": (None, [vp, i64, i64, i64] + u8v + [C.POINTER(ci)]),
+        "pc_rate_strerror": (C.c_char_p, [ci]),
+    }
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise ImportError(f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                              "(hipcc --offload-arch=gfx950).  progressivecodec_amd has no CPU fallback.")
-        L = C.CDLL(LIB_PATH)
-        i64, vp, ci = C.c_int64, C.c_void_p, C.c_int
-        u8v = [vp, ci, i64, i64]                                        # a u8 view: pointer, layout, plane / row stride in bytes
-        L.pc_rate_workspace_size.restype = C.c_size_t
-        L.pc_rate_workspace_size.argtypes = [ci, ci]
-        L.pc_rate_tile_sse_u8.argtypes = [vp, i64, i64, i64] + [ci] * 7 + u8v + [vp, C.c_size_t, vp, vp]
-        L.pc_rate_plan.argtypes = [vp, i64, i64, i64] + u8v + [C.POINTER(ci)]
-        L.pc_rate_strerror.restype = C.c_char_p
-        L.pc_rate_strerror.argtypes = [ci]
-        _lib = L
-    return _lib
+    return _imagelib.load(LIB_PATH, _prototypes)
 
 
-class RateError(RuntimeError):
-    def __init__(self, code, where=""):
-        L = lib()
-        hip = L.pc_rate_last_hip_error() if code == PC_ERR_HIP else 0
-        super().__init__(f"{where}: {ERRORS.get(code, code)} ({L.pc_rate_strerror(code).decode()})" + (f" hipError={hip}" if hip else ""))
+class RateError(_imagelib.ImageLibError):
+    _lib, _prefix = staticmethod(lib), "pc_rate"
 
 
 #: what encode_tiled_to_size decided: levels[t] (index into the quality list), rates[t][l] (bytes tile t costs at level l, its table

@@ -2,7 +2,7 @@
  * DESIGN.md section 12.
  *
  * Kept apart from libpc_tiles.so, as that is from libpc_pixels.so and libpcodec.so: nothing here is part of the codec's numeric
- * contract, byte strings or profiles, and no library of the image domain depends on another.  Plain C, the conventions of
+ * contract, byte strings or profiles, and no library of the image domain links another.  Plain C, the conventions of
  * pc_tiles.h: device pointers, int64 strides, status codes PC_OK / PC_ERR_* (pcodec.h), `stream` is a hipStream_t passed as void*
  * (NULL = default stream).  No call allocates device memory or synchronises the host.  Every argument is checked before the first
  * HIP call; a call that returns PC_ERR_ARG has launched nothing.  All offsets are 64-bit.

@@ -8,37 +8,23 @@
 // path (WIDE: a 128-bit word of floats, a 32-bit word of bytes; else float by float and byte by byte) only changes the load
 // instructions.  Everything that is added is an integer: a thread's sums, the wave tree, the waves of a block, then final_kernel over
 // a tile's block partials.  No floats are accumulated, no atomics.
-#include <hip/hip_runtime.h>
-
-#include <atomic>
-#include <cstdint>
+#include "pc_image_host.h"
+#include "pc_reduce.h"
+#include "pc_tile_grid.h"
 
 #include "pc_rate.h"
 
-static std::atomic<int> g_last_hip{0};
-#define HIPCHK(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { g_last_hip = (int)_e; return PC_ERR_HIP; } } while (0)
-
 namespace {
 
-constexpr int NT = 256;                  // threads per block (4 waves)
 constexpr int ITEMS = 4;                 // work items per thread
 constexpr int BLOCK_ITEMS = NT * ITEMS;
 constexpr int T_MAX = 2048;              // T^4 * 65025 < 2^60: the sums fit 63 bits
-
-typedef unsigned long long u64;
 
 struct U8 {                              // a u8 view (pc_rate.h), strides in bytes
     const uint8_t* p;
     int layout;
     int64_t sp, sr;
 };
-
-struct F32 {                             // a float tile set, strides in elements
-    const float* p;
-    int64_t st, sc, sh;
-};
-
-inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 // The bytes of pixels x0 .. x0 + n - 1 of row y: v[c][i]; the other lanes read as 0 and are not addressed.
 template <bool WIDE>
@@ -74,21 +60,12 @@ __device__ __forceinline__ void load_px(const U8& s, int64_t y, int64_t x0, int 
     }
 }
 
-// The numerator over den of the weight tile i of n gives local coordinate u along an axis (pc_rate.h).
-__device__ __forceinline__ unsigned axis_weight(int i, int n, int u, int S, int O, int den)
-{
-    if (i > 0 && u < O) return (unsigned)(2 * u + 1);
-    if (i < n - 1 && u >= S) return (unsigned)(2 * (O - 1 - (u - S)) + 1);
-    return (unsigned)den;
-}
-
 // Block b of tile t is block t * bpt + b: the items b * BLOCK_ITEMS .. of the tile, item -> (row r, group g), tile columns 4g .. 4g+3.
 // partials[(t * bpt + b) * 3 + c].
 template <bool WIDE>
 __global__ __launch_bounds__(NT) void sse_kernel(F32 x, U8 ref, int H, int W, int S, int O, int ny, int nx, int first_tile, int trunc,
                                                  int G4, int bpt, u64* __restrict__ partials)
 {
-    __shared__ u64 red[NT / 64][3];
     const int t = (int)(blockIdx.x / (unsigned)bpt), b = (int)(blockIdx.x - (unsigned)t * (unsigned)bpt);
     const int tg = first_tile + t, i = tg / nx, j = tg - i * nx;
     const int den = O > 0 ? 2 * O : 1;
@@ -130,64 +107,16 @@ __global__ __launch_bounds__(NT) void sse_kernel(F32 x, U8 ref, int H, int W, in
             }
         }
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-#pragma unroll
-        for (int ch = 0; ch < 3; ++ch) su[ch] += __shfl_down(su[ch], off, 64);
-    }
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int ch = 0; ch < 3; ++ch) red[threadIdx.x >> 6][ch] = su[ch];
-    }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        const int ch = threadIdx.x;
-        u64 u = red[0][ch];
-        for (int wv = 1; wv < NT / 64; ++wv) u += red[wv][ch];
-        partials[(int64_t)blockIdx.x * 3 + ch] = u;
-    }
+    block_reduce<Sum>(su, partials + (int64_t)blockIdx.x * 3);
 }
 
 // One wave per tile: its bpt block partials, lane l taking l, l + 64, ..., then the wave tree.
 __global__ __launch_bounds__(64) void final_kernel(const u64* __restrict__ p, int bpt, u64* __restrict__ out)
 {
-    const int64_t t = blockIdx.x;
-    u64 su[3] = {0ull, 0ull, 0ull};
-    for (int b = threadIdx.x; b < bpt; b += 64) {
-#pragma unroll
-        for (int ch = 0; ch < 3; ++ch) su[ch] += p[(t * bpt + b) * 3 + ch];
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-#pragma unroll
-        for (int ch = 0; ch < 3; ++ch) su[ch] += __shfl_down(su[ch], off, 64);
-    }
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int ch = 0; ch < 3; ++ch) out[t * 3 + ch] = su[ch];
-    }
+    row_final<Sum, 3>(p, bpt, out);
 }
 
 bool layout_ok(int layout) { return layout == PC_RATE_HWC || layout == PC_RATE_CHW; }
-
-int64_t axis_tiles(int L, int T, int S) { return L <= T ? 1 : cdiv((int64_t)L - T, S) + 1; }
-
-struct Geo {
-    int S, ny, nx;
-};
-
-// pc_tiles.h's geometry, with T <= T_MAX
-bool geo_of(int H, int W, int T, int O, Geo& g)
-{
-    if (H < 1 || W < 1 || T < 64 || T % 64 || T > T_MAX || O < 0 || O % 4 || O > T / 2) return false;
-    const int S = T - O;
-    const int64_t ny = axis_tiles(H, T, S), nx = axis_tiles(W, T, S);
-    if (ny * nx > INT32_MAX) return false;
-    g.S = S;
-    g.ny = (int)ny;
-    g.nx = (int)nx;
-    return true;
-}
 
 // Blocks per tile and in all; false for what the call refuses.
 bool blocks_of(int T, int n_tiles, int& bpt, int64_t& blocks)
@@ -198,13 +127,10 @@ bool blocks_of(int T, int n_tiles, int& bpt, int64_t& blocks)
     return blocks <= INT32_MAX;
 }
 
-bool mult4(int64_t v) { return v % 4 == 0; }
-
 // The one place that decides the access path: the call launches from it, pc_rate_plan reports it.
 bool wide_path(const void* x, int64_t st, int64_t sc, int64_t sh, const void* ref, int layout, int64_t rp, int64_t rr)
 {
-    return reinterpret_cast<uintptr_t>(x) % 16 == 0 && mult4(st) && mult4(sc) && mult4(sh) && reinterpret_cast<uintptr_t>(ref) % 4 == 0 &&
-           mult4(rr) && (layout == PC_RATE_HWC || mult4(rp));
+    return f32_wide(x, st, sc, sh) && aligned(ref, 4) && mult4(rr) && (layout == PC_RATE_HWC || mult4(rp));
 }
 
 }  // namespace
@@ -231,14 +157,14 @@ extern "C" int pc_rate_tile_sse_u8(const float* x, int64_t sxt, int64_t sxc, int
     Geo g;
     int bpt;
     int64_t blocks;
-    if (!geo_of(H, W, T, O, g) || !blocks_of(T, n_tiles, bpt, blocks)) return PC_ERR_ARG;
+    if (!geo_of(H, W, T, O, T_MAX, g) || !blocks_of(T, n_tiles, bpt, blocks)) return PC_ERR_ARG;
     if (first_tile < 0 || (int64_t)first_tile + n_tiles > (int64_t)g.ny * g.nx) return PC_ERR_ARG;
-    if (!x || reinterpret_cast<uintptr_t>(x) % 4 || sxh < T || sxc < 1 || sxt < 1) return PC_ERR_ARG;
+    if (!x || !aligned(x, 4) || sxh < T || sxc < 1 || sxt < 1) return PC_ERR_ARG;
     if (rounding != PC_RATE_NEAREST && rounding != PC_RATE_TRUNC) return PC_ERR_ARG;
     if (!ref || !layout_ok(ref_layout)) return PC_ERR_ARG;
     const bool chw = ref_layout == PC_RATE_CHW;
     if (r_row < (chw ? (int64_t)W : 3 * (int64_t)W) || (chw && r_plane < 1)) return PC_ERR_ARG;
-    if (!workspace || reinterpret_cast<uintptr_t>(workspace) % 8 || !out || reinterpret_cast<uintptr_t>(out) % 8) return PC_ERR_ARG;
+    if (!workspace || !aligned(workspace, 8) || !out || !aligned(out, 8)) return PC_ERR_ARG;
     if (workspace_bytes < (size_t)blocks * 3 * sizeof(u64)) return PC_ERR_ARG;
     const bool wide = wide_path(x, sxt, sxc, sxh, ref, ref_layout, r_plane, r_row);
     const F32 xv{x, sxt, sxc, sxh};

@@ -38,58 +38,46 @@ rate.py's (PCT2).
 """
 import collections
 import ctypes as C
-import os
 import struct
 
-from ._lib import ERRORS, PC_OK
+from . import _imagelib
+from ._lib import PC_OK
 from .container import ContainerError
 from .pixels import LAYOUTS, ROUNDINGS, Distortion, _hw, _u8_view
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_HERE, "libpc_tiles.so")
+LIB_PATH = _imagelib.lib_path("tiles")
 
 #: every symbol tiles_csrc/pc_tiles.h declares
 EXPORTS = ["pc_tiles_grid", "pc_tiles_cut_u8", "pc_tiles_stitch_workspace_size", "pc_tiles_stitch_u8", "pc_tiles_plan",
            "pc_tiles_strerror", "pc_tiles_last_hip_error"]
 
 CUT, STITCH = 0, 1                        # pc_tiles_plan's `op`
-PC_ERR_HIP = -6                           # pcodec.h
-
 MAGIC = b"PCT1"
 MAGIC2 = b"PCT2"                          # one level per tile, tiles may differ in quality
 VERSION = 1
 _HEAD = "<BIIIIIII"                       # version, contract id, H, W, T, O, ny, nx
 HEADER_BYTES = 4 + struct.calcsize(_HEAD)
 
-_lib = None
+
+def _prototypes():
+    i64, vp, ci = C.c_int64, C.c_void_p, C.c_int
+    u8v = [vp, ci, i64, i64]                                        # a u8 view: pointer, layout, plane / row stride in bytes
+    return {
+        "pc_tiles_grid": (None, [ci, ci, ci, ci, C.POINTER(ci), C.POINTER(ci)]),
+        "pc_tiles_cut_u8": (None, u8v + [ci] * 8 + [vp, vp]),
+        "pc_tiles_stitch_workspace_size": (C.c_size_t, [ci, ci, ci]),
+        "pc_tiles_stitch_u8": (None, [vp, i64, i64, i64] + [ci] * 13 + u8v + u8v + [vp, C.c_size_t, vp, vp, vp]),
+        "pc_tiles_plan": (None, [ci] + u8v + [vp, i64, i64, i64, ci] + u8v + [C.POINTER(ci)]),
+        "pc_tiles_strerror": (C.c_char_p, [ci]),
+    }
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise ImportError(f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                              "(hipcc --offload-arch=gfx950).  progressivecodec_amd has no CPU fallback.")
-        L = C.CDLL(LIB_PATH)
-        i64, vp, ci = C.c_int64, C.c_void_p, C.c_int
-        u8v = [vp, ci, i64, i64]                                        # a u8 view: pointer, layout, plane / row stride in bytes
-        L.pc_tiles_grid.argtypes = [ci, ci, ci, ci, C.POINTER(ci), C.POINTER(ci)]
-        L.pc_tiles_cut_u8.argtypes = u8v + [ci] * 8 + [vp, vp]
-        L.pc_tiles_stitch_workspace_size.restype = C.c_size_t
-        L.pc_tiles_stitch_workspace_size.argtypes = [ci, ci, ci]
-        L.pc_tiles_stitch_u8.argtypes = [vp, i64, i64, i64] + [ci] * 13 + u8v + u8v + [vp, C.c_size_t, vp, vp, vp]
-        L.pc_tiles_plan.argtypes = [ci] + u8v + [vp, i64, i64, i64, ci] + u8v + [C.POINTER(ci)]
-        L.pc_tiles_strerror.restype = C.c_char_p
-        L.pc_tiles_strerror.argtypes = [ci]
-        _lib = L
-    return _lib
+    return _imagelib.load(LIB_PATH, _prototypes)
 
 
-class TilesError(RuntimeError):
-    def __init__(self, code, where=""):
-        L = lib()
-        hip = L.pc_tiles_last_hip_error() if code == PC_ERR_HIP else 0
-        super().__init__(f"{where}: {ERRORS.get(code, code)} ({L.pc_tiles_strerror(code).decode()})" + (f" hipError={hip}" if hip else ""))
+class TilesError(_imagelib.ImageLibError):
+    _lib, _prefix = staticmethod(lib), "pc_tiles"
 
 
 class TileGrid(collections.namedtuple("TileGrid", "H W T O ny nx ty0 tx0 nty ntx")):

@@ -8,15 +8,10 @@
 // changes the load and store instructions, never which thread handles which pixel or in which order it adds: the bits are the same
 // on both.  The distortion sums run in a fixed order (thread, wave tree, waves in order, then final_kernel over the block partials),
 // no atomics.
-#include <hip/hip_runtime.h>
-
-#include <atomic>
-#include <cstdint>
+#include "pc_image_host.h"
+#include "pc_tile_grid.h"
 
 #include "pc_tiles.h"
-
-static std::atomic<int> g_last_hip{0};
-#define HIPCHK(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { g_last_hip = (int)_e; return PC_ERR_HIP; } } while (0)
 
 namespace {
 
@@ -35,17 +30,10 @@ struct U8 {                              // a u8 view (pc_tiles.h), strides in b
     int64_t sp, sr;
 };
 
-struct F32 {                             // a float tile set, strides in elements
-    const float* p;
-    int64_t st, sc, sh;
-};
-
 struct Partial {                         // one block's sums per channel
     double f[3];
     unsigned long long u[3];
 };
-
-inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 // The bytes of pixels x0 + lo .. x0 + hi - 1 of row y: v[c][i]; the other lanes read as 0.  x0 may lie up to three pixels before the
 // view's first column (then lo > 0): only the lanes lo .. hi - 1 are addressed.
@@ -371,38 +359,6 @@ bool view_ok(const void* p, int layout, int64_t sp, int64_t sr, int h, int w, bo
     return true;
 }
 
-int64_t axis_tiles(int L, int T, int S) { return L <= T ? 1 : cdiv((int64_t)L - T, S) + 1; }
-
-// The geometry every call shares (pc_tiles.h): T, O in range and the grid of an H x W image within 32 bits.
-struct Geo {
-    int S, ny, nx;
-};
-
-bool geo_of(int H, int W, int T, int O, Geo& g)
-{
-    if (H < 1 || W < 1 || T < 64 || T % 64 || O < 0 || O % 4 || O > T / 2) return false;
-    const int S = T - O;
-    const int64_t ny = axis_tiles(H, T, S), nx = axis_tiles(W, T, S);
-    if (ny * nx > INT32_MAX) return false;
-    g.S = S;
-    g.ny = (int)ny;
-    g.nx = (int)nx;
-    return true;
-}
-
-bool rect_ok(const Geo& g, int ty0, int tx0, int nty, int ntx)
-{
-    return ty0 >= 0 && tx0 >= 0 && nty >= 1 && ntx >= 1 && (int64_t)ty0 + nty <= g.ny && (int64_t)tx0 + ntx <= g.nx;
-}
-
-// The first and the last tile along an axis of n tiles that cover pixel p.
-int last_tile(int p, int S, int n) { return p / S < n - 1 ? p / S : n - 1; }
-int first_tile(int p, int S, int O, int n)
-{
-    const int i = last_tile(p, S, n);
-    return i > 0 && p - i * S < O ? i - 1 : i;
-}
-
 // The item space of a stitch: rows x the image-aligned four-column groups that meet [x0, x0 + w).
 struct Items {
     int G, blocks;
@@ -420,18 +376,11 @@ bool items_of(int x0, int h, int w, Items& it)
     return true;
 }
 
-bool mult4(int64_t v) { return v % 4 == 0; }
-
 // The alignment of a u8 view as the wide path needs it; `shift`: bytes from the pointer back to the first work item's column 0.
 bool u8_wide(const void* p, int layout, int64_t sp, int64_t sr, int64_t shift)
 {
     const int64_t a = (int64_t)(reinterpret_cast<uintptr_t>(p) % 4) - shift % 4;
     return mult4(a) && mult4(sr) && (layout == PC_TILES_HWC || mult4(sp));
-}
-
-bool f32_wide(const void* p, int64_t ft, int64_t fc, int64_t fh)
-{
-    return reinterpret_cast<uintptr_t>(p) % 16 == 0 && mult4(ft) && mult4(fc) && mult4(fh);
 }
 
 // The one place that decides the access path: the calls launch from it, pc_tiles_plan reports it.
@@ -449,7 +398,7 @@ bool wide_path(int op, const void* u8, int layout, int64_t sp, int64_t sr, const
 extern "C" int pc_tiles_grid(int H, int W, int T, int O, int* ny, int* nx)
 {
     Geo g;
-    if (!ny || !nx || !geo_of(H, W, T, O, g)) return PC_ERR_ARG;
+    if (!ny || !nx || !geo_of(H, W, T, O, INT_MAX, g)) return PC_ERR_ARG;
     *ny = g.ny;
     *nx = g.nx;
     return PC_OK;
@@ -473,8 +422,8 @@ extern "C" int pc_tiles_cut_u8(const uint8_t* src, int layout, int64_t s_plane, 
                                int nty, int ntx, float* dst, void* stream)
 {
     Geo g;
-    if (!geo_of(H, W, T, O, g) || !rect_ok(g, ty0, tx0, nty, ntx)) return PC_ERR_ARG;
-    if (!dst || reinterpret_cast<uintptr_t>(dst) % 4 || !view_ok(src, layout, s_plane, s_row, H, W, false)) return PC_ERR_ARG;
+    if (!geo_of(H, W, T, O, INT_MAX, g) || !rect_ok(g, ty0, tx0, nty, ntx)) return PC_ERR_ARG;
+    if (!dst || !aligned(dst, 4) || !view_ok(src, layout, s_plane, s_row, H, W, false)) return PC_ERR_ARG;
     const int G4 = T / 4;
     const int64_t tile_items = (int64_t)T * G4, tiles = (int64_t)nty * ntx;
     if (tile_items > INT32_MAX || tiles > INT32_MAX / 3) return PC_ERR_ARG;
@@ -506,8 +455,8 @@ extern "C" int pc_tiles_stitch_u8(const float* x, int64_t sxt, int64_t sxc, int6
 {
     Geo g;
     Items it;
-    if (!geo_of(H, W, T, O, g) || !rect_ok(g, ty0, tx0, nty, ntx)) return PC_ERR_ARG;
-    if (!x || reinterpret_cast<uintptr_t>(x) % 4 || sxh < T || sxc < 1 || sxt < 1) return PC_ERR_ARG;
+    if (!geo_of(H, W, T, O, INT_MAX, g) || !rect_ok(g, ty0, tx0, nty, ntx)) return PC_ERR_ARG;
+    if (!x || !aligned(x, 4) || sxh < T || sxc < 1 || sxt < 1) return PC_ERR_ARG;
     if (y0 < 0 || x0 < 0 || h < 1 || w < 1 || (int64_t)y0 + h > H || (int64_t)x0 + w > W || !items_of(x0, h, w, it)) return PC_ERR_ARG;
     // every tile that covers a pixel of the window lies in the rectangle
     if (first_tile(y0, g.S, O, g.ny) < ty0 || last_tile(y0 + h - 1, g.S, g.ny) >= ty0 + nty) return PC_ERR_ARG;
@@ -516,8 +465,8 @@ extern "C" int pc_tiles_stitch_u8(const float* x, int64_t sxt, int64_t sxc, int6
     if (dst ? !view_ok(dst, dst_layout, d_plane, d_row, h, w, true) : !ref) return PC_ERR_ARG;          // sums only: no image is written
     if (ref) {
         if (!view_ok(ref, ref_layout, r_plane, r_row, h, w, false)) return PC_ERR_ARG;
-        if (!workspace || reinterpret_cast<uintptr_t>(workspace) % 8) return PC_ERR_ARG;
-        if (!sse_u8 || reinterpret_cast<uintptr_t>(sse_u8) % 8 || !sse_f || reinterpret_cast<uintptr_t>(sse_f) % 8) return PC_ERR_ARG;
+        if (!workspace || !aligned(workspace, 8)) return PC_ERR_ARG;
+        if (!sse_u8 || !aligned(sse_u8, 8) || !sse_f || !aligned(sse_f, 8)) return PC_ERR_ARG;
         if (workspace_bytes < (size_t)it.blocks * sizeof(Partial)) return PC_ERR_ARG;
     }
     const bool wide = wide_path(PC_TILES_STITCH, dst, dst_layout, d_plane, d_row, x, sxt, sxc, sxh, x0, ref, ref_layout, r_plane, r_row);

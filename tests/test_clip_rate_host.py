@@ -13,6 +13,7 @@ import torch
 from tests import clip_rate_contract as RC2
 from tests import clips_contract as CC
 from tests import frames_contract as FC
+from tests import image_shared
 from tests.test_clips_host import SOURCE
 from tests.test_frames_host import fake_frame
 from tests.test_tiles_host import blob
@@ -298,16 +299,16 @@ def test_library_exports_every_declared_function():
     import bench
     import inspect
     assert "clip_rate" not in inspect.getsource(bench.source_hash)
-    mk = "".join(l for l in open(os.path.join(ROOT, "progressivecodec_amd", "clip_rate_csrc", "Makefile")) if not l.startswith("#"))
+    mk = image_shared.build_rule("clip_rate")                                             # image_csrc/lib.mk, which the library's Makefile includes
     assert "-ffp-contract=off" in mk
     assert not re.search(r"-lpc|libpc(odec|_pixels|_tiles|_rate|_metrics|_frames|_frame_tiles|_frame_rate|_clips)\b", mk)
     top = open(os.path.join(ROOT, "progressivecodec_amd", "csrc", "Makefile")).read()
     assert re.search(r"^all:.*\bclip_rate\b", top, re.M) and re.search(r"^\.PHONY:.*\bclip_rate\b", top, re.M)
     assert "$(MAKE) -C ../clip_rate_csrc clean" in top and re.search(r"^clip_rate:\n\t\$\(MAKE\) -C \.\./clip_rate_csrc$", top, re.M)
-    # the frame is pc_frame_rate.h's and pc_frames.h's, member for member: frames.Frame serves this library, too
-    body = lambda h, name: re.sub(r"/\*.*?\*/", "", re.search(r"typedef struct %s \{(.*?)\}" % name, h, re.S).group(1), flags=re.S).split()   # noqa: E731
-    assert body(hdr, "pc_cr_frame") == body(open(os.path.join(ROOT, "progressivecodec_amd", "frames_csrc", "pc_frames.h")).read(), "pc_frame")
-    assert body(hdr, "pc_cr_frame") == body(open(os.path.join(ROOT, "progressivecodec_amd", "frame_rate_csrc", "pc_frame_rate.h")).read(), "pc_fr_frame")
+    # the frame is the one record of image_csrc/pc_yuv_frame.h, as pc_frame_rate.h's and pc_frames.h's are: frames.Frame serves this
+    # library, too
+    image_shared.assert_frame_is_shared(hdr, "pc_cr_frame")
+    image_shared.assert_frame_is_shared(open(os.path.join(ROOT, "progressivecodec_amd", "frame_rate_csrc", "pc_frame_rate.h")).read(), "pc_fr_frame")
     # no atomics, no inline assembly in the kernels
     src = open(os.path.join(ROOT, "progressivecodec_amd", "clip_rate_csrc", "pc_clip_rate.hip")).read()
     code = re.sub(r"//[^\n]*", "", src)

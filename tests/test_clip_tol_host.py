@@ -13,6 +13,7 @@ import torch
 from tests import clip_tol_contract as TOL
 from tests import clips_contract as CC
 from tests import frames_contract as FC
+from tests import image_shared
 from tests import tiles_contract as TC
 from tests.test_frames_host import fake_frame
 
@@ -199,17 +200,15 @@ def test_library_exports_every_declared_function():
     import bench
     import inspect
     assert "clip_tol" not in inspect.getsource(bench.source_hash)
-    mk = "".join(l for l in open(os.path.join(ROOT, "progressivecodec_amd", "clip_tol_csrc", "Makefile")) if not l.startswith("#"))
-    ref = "".join(l for l in open(os.path.join(ROOT, "progressivecodec_amd", "clip_rate_csrc", "Makefile")) if not l.startswith("#"))
-    assert mk == ref.replace("clip_rate", "clip_tol")                                # clip_rate_csrc's flags, word for word
+    mk = image_shared.build_rule("clip_tol")                                             # image_csrc/lib.mk, which the library's Makefile includes
+    assert mk == image_shared.build_rule("clip_rate")                                # clip_rate_csrc's rule and flags: the same file
     assert "-ffp-contract=off" in mk and "--offload-arch=$(ARCH)" in mk and "-fvisibility=hidden" in mk
     assert not re.search(r"-lpc|libpc(odec|_pixels|_tiles|_rate|_metrics|_frames|_frame_tiles|_frame_rate|_clips|_clip_rate)\b", mk)
     top = open(os.path.join(ROOT, "progressivecodec_amd", "csrc", "Makefile")).read()
     assert re.search(r"^all:.*\bclip_tol\b", top, re.M) and re.search(r"^\.PHONY:.*\bclip_tol\b", top, re.M)
     assert "$(MAKE) -C ../clip_tol_csrc clean" in top and re.search(r"^clip_tol:\n\t\$\(MAKE\) -C \.\./clip_tol_csrc$", top, re.M)
-    # the frame is pc_frames.h's, member for member: frames.Frame serves this library, too
-    body = lambda h, name: re.sub(r"/\*.*?\*/", "", re.search(r"typedef struct %s \{(.*?)\}" % name, h, re.S).group(1), flags=re.S).split()   # noqa: E731
-    assert body(hdr, "pc_ct_frame") == body(open(os.path.join(ROOT, "progressivecodec_amd", "frames_csrc", "pc_frames.h")).read(), "pc_frame")
+    # the frame is the one record of image_csrc/pc_yuv_frame.h, as pc_frames.h's is: frames.Frame serves this library, too
+    image_shared.assert_frame_is_shared(hdr, "pc_ct_frame")
     # no atomics, no inline assembly in the kernels
     src = open(os.path.join(ROOT, "progressivecodec_amd", "clip_tol_csrc", "pc_clip_tol.hip")).read()
     code = re.sub(r"//[^\n]*", "", src)

@@ -14,6 +14,7 @@ import torch
 
 from tests import frame_tiles_contract as GC
 from tests import frames_contract as FC
+from tests import image_shared
 from tests import tiles_contract as TC
 from tests.test_frames_host import fake_frame
 from tests.test_tiles_host import blob, pct1
@@ -157,14 +158,13 @@ def test_library_exports_every_declared_function():
     import bench
     import inspect
     assert "frame_tiles" not in inspect.getsource(bench.source_hash)
-    mk = "".join(l for l in open(os.path.join(ROOT, "progressivecodec_amd", "frame_tiles_csrc", "Makefile")) if not l.startswith("#"))
+    mk = image_shared.build_rule("frame_tiles")                                             # image_csrc/lib.mk, which the library's Makefile includes
     assert "-ffp-contract=off" in mk and not re.search(r"-lpc|libpc(odec|_pixels|_tiles|_rate|_metrics|_frames)\b", mk)
     top = open(os.path.join(ROOT, "progressivecodec_amd", "csrc", "Makefile")).read()
     assert re.search(r"^all:.*\bframe_tiles\b", top, re.M) and re.search(r"^\.PHONY:.*\bframe_tiles\b", top, re.M)
     assert "$(MAKE) -C ../frame_tiles_csrc clean" in top
-    # the frame is pc_frames.h's, member for member: frames.Frame serves both libraries
-    body = lambda h, name: re.sub(r"/\*.*?\*/", "", re.search(r"typedef struct %s \{(.*?)\}" % name, h, re.S).group(1), flags=re.S).split()   # noqa: E731
-    assert body(hdr, "pc_ft_frame") == body(open(os.path.join(ROOT, "progressivecodec_amd", "frames_csrc", "pc_frames.h")).read(), "pc_frame")
+    # the frame is the one record of image_csrc/pc_yuv_frame.h, as pc_frames.h's is: frames.Frame serves both libraries
+    image_shared.assert_frame_is_shared(hdr, "pc_ft_frame")
 
 
 def test_workspace_size_is_the_documented_formula():
