@@ -93,14 +93,14 @@ def scan_raw(table, fmt, up, H, W, O, tol, n, n_frames=None, nbytes=None, T_=T):
     rows = max(nf, 0) + 2
     source = torch.full((rows, n), POISON32, dtype=torch.int32, device=DEV)
     stats = torch.full((rows, n, 3, 3), POISON64, dtype=torch.int64, device=DEV)
-    need = L.pc_clip_tol_workspace_size(T, n)
+    need = L.pc_clip_tol_workspace_size(T_, n)
     ws = torch.full((need // 8 + 2,), POISON64, dtype=torch.int64, device=DEV)
     host, dev = ct._frame_table(table, torch.device(DEV))
     rc = L.pc_clip_tol_scan(host, dev.data_ptr(), nf, frames.FORMATS.get(fmt, fmt), frames.UPSAMPLES.get(up, up), H, W, T_, O,
                             (C.c_int * 3)(*tol[0]), (C.c_int * 3)(*tol[1]), tol[2], ws.data_ptr(), need if nbytes is None else nbytes,
                             source[1:].data_ptr(), stats[1:].data_ptr(), stream())
     h = ws.cpu().view(torch.int32)
-    npart = 18 * n * (T * T // 4096 + 1)                                  # 32-bit words of partials; then n of anchors
+    npart = 18 * n * (T_ * T_ // 4096 + 1)                                 # 32-bit words of partials; then n of anchors
     if rc != 0:
         ws_ok = bool((h == POISON32).all())
     else:

@@ -85,17 +85,17 @@ def frame_pair(fmt, H, W, kind, seed):
     return cur, prev
 
 
-def changes_raw(cur, prev, fmt, up, H, W, O, first, n, nbytes=None):
+def changes_raw(cur, prev, fmt, up, H, W, O, first, n, nbytes=None, size=T):
     """pc_clips_tile_changes -> (status, the [n + 2, 3] buffer whose rows 1 .. n are `out`, poisoned beforehand, whether every partial
     of the workspace and no word after it was written -- or, for a refused call, none at all).  fmt and up: names, or raw ids for the
     calls that are to be refused."""
     from progressivecodec_amd import frames
     L = CL().lib()
     buf = torch.full((max(n, 0) + 2, 3), POISON64, dtype=torch.int64, device=DEV)
-    need = L.pc_clips_changes_workspace_size(T, n)
+    need = L.pc_clips_changes_workspace_size(size, n)
     ws = torch.full((need // 8 + 1,), POISON64, dtype=torch.int64, device=DEV)
     a, b = frames._frame_struct(list(cur)), frames._frame_struct(list(prev))
-    rc = L.pc_clips_tile_changes(C.byref(a), C.byref(b), frames.FORMATS.get(fmt, fmt), frames.UPSAMPLES.get(up, up), H, W, T, O, first, n,
+    rc = L.pc_clips_tile_changes(C.byref(a), C.byref(b), frames.FORMATS.get(fmt, fmt), frames.UPSAMPLES.get(up, up), H, W, size, O, first, n,
                                  ws.data_ptr(), need if nbytes is None else nbytes, buf[1:].data_ptr(), stream())
     h = ws.cpu()
     return rc, buf, bool(h[-1] == POISON64 and ((h[:-1] != POISON64).all() if rc == 0 else (h == POISON64).all()))
