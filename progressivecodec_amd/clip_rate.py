@@ -25,7 +25,7 @@ level; tiles may differ in quality.  What PCT2 is to PCT1.
 
 There is no CPU fallback: CPU tensors raise ValueError before any device call.  Everything runs on the current stream of the tensors'
 device.  Out of scope: per-frame byte caps and constant bitrate, a target PSNR (the dual problem), a tolerance inside
-encode_clip_to_size (clip_tol.py has it for clips.encode_clip; the reuse identity above does not hold under it), inter-frame
+encode_clip_to_size (the reuse identity above does not hold under it: clip_tol_rate.py is that encoder), inter-frame
 prediction, batching the decode across frames.
 """
 import collections
@@ -273,22 +273,11 @@ def item_weights(items, runs, n_tiles, n_frames, importance=None, frame_weights=
 
 # -- through the codec ---------------------------------------------------------------------------------------------------------------
 
-def encode_clip_to_size(model, frames, qualities, target_bytes, fmt, matrix="bt709", range="limited", upsample="linear", tile=512,
-                        overlap=0, mask_pol="point-based-std", plane_weights=(1, 1, 1), importance=None, frame_weights=None, reuse=True,
-                        max_tiles_per_call=32):
-    """clip -> (PCS2 container of at most target_bytes bytes, ClipRatePlan).  The source table is clips.encode_clip's (one
-    clip_changes and one device-to-host copy; reuse=False makes every tile of every frame an item of its own).  The items -- the
-    tiles that are coded -- are chunked by max_tiles_per_call ACROSS frames; per chunk one cut launch per frame present in it into
-    one batch buffer, model.compress_levels, model.decompress_levels, one pc_clip_rate_sse_jobs call per level for the whole chunk
-    (the frame table and the job list of the whole clip are uploaded once) and container.pack of a single level per item and level.
-    Every item then gets the level rate.allocate picks from the bytes each level costs and the distortion it leaves (the planes
-    weighted by plane_weights = (wY, wCb, wCr), non-negative ints), weighted by importance[t] (one positive number per tile, [ny][nx]
-    or flat) times the sum of frame_weights[k] (one positive number per frame) over the frames that show it, under the budget
-    target_bytes - 42 - 16 * F * ny * nx.  ValueError, its message holding the minimum, if the cheapest level of every item does not
-    fit.  Neither the bytes nor the plan depend on max_tiles_per_call or on how the frames lie in memory; frame_container(buf, k)
-    is a PCG1 container frame_tiles.decode_frame_tiled reads."""
-    import torch
-    from . import container
+def _to_size_arguments(frames, qualities, target_bytes, fmt, matrix, range, upsample, tile, overlap, plane_weights, importance, frame_weights,
+                       max_tiles_per_call):
+    """the argument checks of encode_clip_to_size (clip_tol_rate.encode_clip_to_size comes here, too), in its order and with its
+    messages -> (qualities, step, plane weights, target_bytes, fs (the planes of frame k as batched views), the grid, importance
+    flat or None, frame_weights as a list or None)"""
     qualities = [float(q) for q in qualities]
     if not qualities:
         raise ValueError("at least one level")
@@ -304,7 +293,7 @@ def encode_clip_to_size(model, frames, qualities, target_bytes, fmt, matrix="bt7
     g = clips._grid(H, W, tile, overlap)
     if g.T > max_tile(fmt):
         raise ValueError(f"tile must be at most {max_tile(fmt)} for the distortion sums of {fmt!r} to fit 63 bits, got {g.T}")
-    n, F, nl = g.ny * g.nx, len(fs), len(qualities)
+    n, F = g.ny * g.nx, len(fs)
     if importance is not None:
         importance = list(importance)
         if importance and isinstance(importance[0], (list, tuple)):
@@ -315,23 +304,22 @@ def encode_clip_to_size(model, frames, qualities, target_bytes, fmt, matrix="bt7
         frame_weights = list(frame_weights)
         if len(frame_weights) != F:
             raise ValueError(f"frame_weights needs one number per frame of the clip, {F} in all, got {len(frame_weights)}")
-    if reuse and F > 1:
-        counts = _clip_changes(fs, fmt, g, upsample, 0, n).cpu()
-        source = source_table((counts != 0).any(dim=2).tolist())
-    else:
-        source = [[f] * n for f in _range(F)]
-    items, runs = items_of(source)
-    weights = item_weights(items, runs, n, F, importance, frame_weights)
-    k = coefficients(matrix)
+    return qualities, step, pw, target_bytes, fs, g, importance, frame_weights
+
+
+def _code_items(model, fs, g, items, qualities, fmt, range, upsample, mask_pol, k, step, measure):
+    """The work loop of encode_clip_to_size once the items are known (clip_tol_rate.encode_clip_to_size comes here with its own
+    measure): the items chunked by `step` ACROSS frames; per chunk one cut launch per frame present in it into one batch buffer,
+    model.compress_levels, model.decompress_levels, measure(a, b, decoded) -- the chunk is items[a:a + b], decoded[l]["x_hat"] its
+    tiles at level l; it returns one entry per item of the chunk and is done with the tiles when it returns -- and container.pack
+    of a single level per item and level -> (bufs[i][l], what measure returned, item by item)."""
+    import torch
+    from . import container
     dev = fs[0][0].device
-    CL, L = clips.lib(), lib()
-    bufs, plane_dists = [], []
+    CL = clips.lib()
+    bufs, measured = [], []
     with torch.cuda.device(dev):
-        host, table = _frame_table(fs, dev)
-        djobs = torch.tensor(items, dtype=torch.int32).to(dev)                 # [(f, t)]: the cut takes the tiles, the measure both
-        didx = djobs[:, 1].contiguous()
-        nbytes = L.pc_clip_rate_workspace_size(g.T, min(step, len(items)))
-        ws = torch.empty(nbytes // 8, dtype=torch.int64, device=dev)
+        didx = torch.tensor([t for _, t in items], dtype=torch.int32).to(dev)  # the cut takes the tiles
     for a in _range(0, len(items), step):
         chunk = items[a:a + step]
         b = len(chunk)
@@ -351,17 +339,57 @@ def encode_clip_to_size(model, frames, qualities, target_bytes, fmt, matrix="bt7
         shape = datas[0]["shape"]
         decoded = model.decompress_levels(strings, shape, qualities, mask_pol)
         with torch.cuda.device(dev):
-            d = torch.empty((nl, b, 3), dtype=torch.int64, device=dev)
-            st = torch.cuda.current_stream(dev).cuda_stream
-            for l, o in enumerate(decoded):                                    # one call per level, ordered on the stream: one workspace
-                xh = _fit_tiles(o["x_hat"], g.T)
-                _sse_jobs_into(L, xh, g, fmt, range, k, host, table, F, djobs[a:].data_ptr(), b, ws, nbytes, d[l], st)
-            d = d.tolist()                                                     # [levels][b][3]; synchronises: xh may go
+            measured += measure(a, b, decoded)
         del decoded
         for m in _range(b):
             bufs.append([container.pack([strings[l]], shape, [q], image_size=(g.T, g.T), mask_pol=mask_pol, image_index=m)
                          for l, q in enumerate(qualities)])
-            plane_dists.append([[int(v) for v in d[l][m]] for l in _range(nl)])
+    return bufs, measured
+
+
+def encode_clip_to_size(model, frames, qualities, target_bytes, fmt, matrix="bt709", range="limited", upsample="linear", tile=512,
+                        overlap=0, mask_pol="point-based-std", plane_weights=(1, 1, 1), importance=None, frame_weights=None, reuse=True,
+                        max_tiles_per_call=32):
+    """clip -> (PCS2 container of at most target_bytes bytes, ClipRatePlan).  The source table is clips.encode_clip's (one
+    clip_changes and one device-to-host copy; reuse=False makes every tile of every frame an item of its own).  The items -- the
+    tiles that are coded -- are chunked by max_tiles_per_call ACROSS frames; per chunk one cut launch per frame present in it into
+    one batch buffer, model.compress_levels, model.decompress_levels, one pc_clip_rate_sse_jobs call per level for the whole chunk
+    (the frame table and the job list of the whole clip are uploaded once) and container.pack of a single level per item and level.
+    Every item then gets the level rate.allocate picks from the bytes each level costs and the distortion it leaves (the planes
+    weighted by plane_weights = (wY, wCb, wCr), non-negative ints), weighted by importance[t] (one positive number per tile, [ny][nx]
+    or flat) times the sum of frame_weights[k] (one positive number per frame) over the frames that show it, under the budget
+    target_bytes - 42 - 16 * F * ny * nx.  ValueError, its message holding the minimum, if the cheapest level of every item does not
+    fit.  Neither the bytes nor the plan depend on max_tiles_per_call or on how the frames lie in memory; frame_container(buf, k)
+    is a PCG1 container frame_tiles.decode_frame_tiled reads."""
+    import torch
+    qualities, step, pw, target_bytes, fs, g, importance, frame_weights = _to_size_arguments(
+        frames, qualities, target_bytes, fmt, matrix, range, upsample, tile, overlap, plane_weights, importance, frame_weights, max_tiles_per_call)
+    n, F, nl = g.ny * g.nx, len(fs), len(qualities)
+    if reuse and F > 1:
+        counts = _clip_changes(fs, fmt, g, upsample, 0, n).cpu()
+        source = source_table((counts != 0).any(dim=2).tolist())
+    else:
+        source = [[f] * n for f in _range(F)]
+    items, runs = items_of(source)
+    weights = item_weights(items, runs, n, F, importance, frame_weights)
+    k = coefficients(matrix)
+    dev = fs[0][0].device
+    L = lib()
+    with torch.cuda.device(dev):
+        host, table = _frame_table(fs, dev)
+        djobs = torch.tensor(items, dtype=torch.int32).to(dev)                 # [(f, t)] of the whole clip, uploaded once
+        nbytes = L.pc_clip_rate_workspace_size(g.T, min(step, len(items)))
+        ws = torch.empty(nbytes // 8, dtype=torch.int64, device=dev)
+
+    def measure(a, b, decoded):
+        d = torch.empty((nl, b, 3), dtype=torch.int64, device=dev)
+        st = torch.cuda.current_stream(dev).cuda_stream
+        for l, o in enumerate(decoded):                                        # one call per level, ordered on the stream: one workspace
+            xh = _fit_tiles(o["x_hat"], g.T)
+            _sse_jobs_into(L, xh, g, fmt, range, k, host, table, F, djobs[a:].data_ptr(), b, ws, nbytes, d[l], st)
+        d = d.tolist()                                                         # [levels][b][3]; synchronises: xh may go
+        return [[[int(v) for v in d[l][m]] for l in _range(nl)] for m in _range(b)]
+    bufs, plane_dists = _code_items(model, fs, g, items, qualities, fmt, range, upsample, mask_pol, k, step, measure)
     del fs
     rates = [[len(p) for p in row] for row in bufs]
     dists = [[pw[0] * v[0] + pw[1] * v[1] + pw[2] * v[2] for v in row] for row in plane_dists]
