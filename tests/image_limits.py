@@ -7,7 +7,9 @@ Four groups of cases (DESIGN.md section 19.1 lists the limit each executes):
      a row of partials with a lane stride of 64, make a second and a fourth trip; and tail-only data, whose only non-zero partial
      is the last of the row (and, for the clip libraries, the halo block after it);
   C  whole pictures of 1026 x 1030: more than 256 block partials per picture, sums past 2^32;
-  D  the cuts at T = 576 and T = 2048.
+  D  the cuts at T = 576 and T = 2048;
+  E  clip_tol_rate (section 20), whose partials are per WAVE and per entry: A and B again -- 4096 wave partials per entry at
+     T = 2048 (64 trips of its final), 1024 at T = 1024 in P010 (16 trips) -- and runs longer than a wave has lanes.
 Expected values are the restatements'; for saturated inputs also the closed forms below in Python ints, and the host test holds
 the two to each other.
 """
@@ -50,7 +52,7 @@ CUT_LARGE = dict(T=2048, O=0, H=4098, W=4098, rect=(1, 1, 1, 1))
 
 #: the largest T each library's header promises, per element width
 T_MAX = {"rate": {8: 2048}, "frame_rate": {8: 2048, 10: 1024}, "clip_rate": {8: 2048, 10: 1024}, "clips": {8: 2048, 10: 2048},
-         "clip_tol": {8: 2048, 10: 2048}}
+         "clip_tol": {8: 2048, 10: 2048}, "clip_tol_rate": {8: 2048, 10: 1024}}
 
 
 # -- closed forms, Python ints -------------------------------------------------------------------------------------------------------
@@ -243,4 +245,59 @@ def stitch_tail(x_equal, T, O, H, W):
         for r in rows:
             for j in range(nx):
                 out[i * nx + j, :, r, :] = flip(x_equal[i * nx + j, :, r, :])
+    return out
+
+
+# -- E: clip_tol_rate ------------------------------------------------------------------------------------------------------------------
+
+#: A: (tile value, tile, run) per job over the table (frame_saturated(fmt, False), frame_saturated(fmt, True), the first again)
+RUN_LIMIT_JOBS = [(0.0, 4, [0, 1, 0]), (1.0, 4, [1, 0]), (0.0, 0, [0])]
+RUN_LIMIT_MIRRORS = (False, True, False)
+#: C: T = 64 on a 100 x 150 picture, three frames; the run lengths of the six jobs, 300 entries in all
+LONG_RUNS = dict(T=64, H=100, W=150, O=16, lengths=(70, 1, 2, 33, 64, 130), tiles=(5, 0, 3, 5, 1, 2))
+
+
+def saturated_errors(fmt, v, mirror):
+    """(eY, eC) of a constant tile of value v (codes 0 or top, co, co in full range) against frame_saturated(fmt, mirror)'s frame"""
+    _, _, co, _, mx = FC.levels(fmt, "full")
+    ty = mx if v else 0
+    fy, fc = (0, mx) if mirror else (mx, 0)
+    return abs(ty - fy), abs(co - fc)
+
+
+def run_limit_case(fmt):
+    """(frames, tile values, tile_ids, runs, the closed-form rows) of A"""
+    c = FRAME_LIMITS[fmt]
+    frames = [frame_saturated(fmt, mirror)[1] for mirror in RUN_LIMIT_MIRRORS]
+    vals, tile_ids, runs = ([j[k] for j in RUN_LIMIT_JOBS] for k in range(3))
+    want = [frame_rate_closed(dict(c, tile=t), *saturated_errors(fmt, v, RUN_LIMIT_MIRRORS[f])) for v, t, run in RUN_LIMIT_JOBS for f in run]
+    return frames, vals, tile_ids, runs, want
+
+
+def run_list(n):
+    """runs over two frames in job_list's style: both frames, a repeat inside a run, out of order, the whole first tile twice with
+    different runs and the clipped last one"""
+    return [n - 1, 0, 1, 0], [[1, 0], [0, 1, 0], [1], [1, 1]]
+
+
+def run_trip_cases():
+    """(T, H, W, O, wide, format): the three overlaps of the second trip in all three formats, the four trips in P010"""
+    s, f = SECOND_TRIP, FOUR_TRIPS
+    out = [(s["T"], s["H"], s["W"], O, wide, fmt) for O, wide in SECOND_TRIP_OVERLAPS for fmt in FC.FORMATS]
+    return out + [(f["T"], f["H"], f["W"], f["O"], True, "p010")]
+
+
+def long_runs():
+    """(tile_ids, runs): six jobs, slots cycling through the three frames with a repeat every fourth entry, each job starting at
+    another slot; one run longer than a wave has lanes, one of exactly 64, and 300 entries in all"""
+    c = LONG_RUNS
+    runs = [[(j - j // 4 + m) % 3 for j in range(n)] for m, n in enumerate(c["lengths"])]
+    return list(c["tiles"]), runs
+
+
+def run_workspace_cases():
+    """(T, n_entries) of every clip_tol_rate case of this table"""
+    out = [(FRAME_LIMITS[fmt]["T"], sum(len(j[2]) for j in RUN_LIMIT_JOBS)) for fmt in FRAME_LIMITS]
+    out += [(c[0], sum(len(r) for r in run_list(4)[1])) for c in run_trip_cases()]
+    out += [(SECOND_TRIP["T"], 4), (LONG_RUNS["T"], sum(LONG_RUNS["lengths"]))]
     return out

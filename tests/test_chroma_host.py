@@ -14,9 +14,11 @@ import numpy as np
 import pytest
 import torch
 
+from tests import chroma_cases as CS
 from tests import chroma_contract as CC
 from tests import frames_contract as FC
 from tests import image_shared
+from tests import pixels_contract as K
 from tests.test_frames_host import pcb1
 from tests.test_image_shared_host import DEFINITIONS
 from tests.test_tiles_host import blob
@@ -589,3 +591,129 @@ def test_the_twelfth_library_keeps_the_rules_of_the_eleven():
     # a library of its own: the codec's source hash does not cover it
     import bench
     assert "chroma" not in inspect.getsource(bench.source_hash) and "_hip" not in inspect.getsource(bench.source_hash)
+
+
+# -- 11. the case table of the GPU matrices and the ledger of instantiations ---------------------------------------------------------
+
+def old_loops(fmt, matrix, rng, sizes):
+    """the loops tests/test_gpu_chroma.py's run_matrix had before it read tests/chroma_cases.py, restated once: per position
+    (siting, size, left, offset, mode, float variant, the ingest's destination offset, [(with image, with reference)])"""
+    out = []
+    for n, (siting, (H, W)) in enumerate(itertools.product(CC.SITINGS, sizes)):
+        left0 = K.geometry(H, W)[3]
+        narrow = n % 2 == 0
+        left, offset, mode, variant = (left0, 1 + n % 3, "loose", "odd") if narrow else (left0 // 8 * 8, 0, "pad4", ("contiguous", "loose4")[n % 4 // 2])
+        emits = [(True, True)] + ([(False, True), (True, False)] if (H, W) == (37, 53) else [])
+        out.append(CS.Case(fmt, matrix, rng, siting, H, W, n, left, offset, mode, variant, int(narrow), ("nearest", "linear"), tuple(emits)))
+    return out
+
+
+def old_cases():
+    sizes = [(1, 1), (2, 3), (3, 2), (37, 53), (64, 64), (67, 130)]
+    out = [c for fmt in sorted(CC.FORMATS) for c in old_loops(fmt, "bt709", "limited", sizes)]
+    for fmt in ["nv16", "p210", "i444"]:
+        for matrix, rng in [("bt601", "full"), ("bt2020", "limited"), ("bt2020", "full"), ("bt709", "full"), ("bt601", "limited")]:
+            out += old_loops(fmt, matrix, rng, [(37, 53), (3, 2)])
+    return out
+
+
+def names(tuples):
+    return sorted("u%d %s %d:%d%s %s%s" % (8 * t[0], "semi" if t[1] else "planar", t[2], t[3], " vco" if len(t) == 7 and t[4] else "",
+                                           "wide" if t[-2 if len(t) == 7 else -1] else "narrow", (" ref" if t[-1] else " image") if len(t) == 7 else "")
+                  for t in tuples)
+
+
+def test_the_table_runs_at_least_what_the_loops_ran():
+    table, old = CS.table(), old_cases()
+    assert len(old) == 12 * 18 + 3 * 5 * 6 and set(old) <= set(table) and len(set(table)) == len(table)
+    assert set(CC.UPSAMPLES) == {"nearest", "linear"}
+    added = [c for c in table if c not in set(old)]
+    assert len(added) == 12 * 4 and all(c.emits == ((True, False),) and not c.ups and not CS.emit_wide(c) for c in added)
+    assert {(c.fmt, c.siting, c.H, c.W) for c in added} == {(f, s, H, W) for f in CC.FORMATS for s in ("centre", "topleft") for H, W in [(37, 53), (3, 2)]}
+    # positions alternate between the paths, and the rule agrees with what the loops asserted case by case: narrow at even positions
+    for c in table:
+        assert CS.emit_wide(c) is (c.n % 2 == 1) and (not c.ups or CS.ingest_wide(c) is (c.n % 2 == 1)), c
+    # the rule itself, each precondition broken alone
+    c = next(c for c in table if c.n % 2 == 1 and (c.H, c.W) == (37, 53))
+    assert CS.emit_wide(c) and CS.ingest_wide(c)
+    assert not CS.emit_wide(c._replace(variant="odd")) and not CS.emit_wide(c._replace(left=c.left + 2)) and CS.emit_wide(c._replace(left=c.left + 4))
+    assert not CS.ingest_wide(c._replace(left=c.left + 4)) and not CS.ingest_wide(c._replace(dst_offset=1)) and not CS.ingest_wide(c._replace(offset=2))
+    assert not CS.emit_wide(c, ref=(0, "loose")) and not CS.emit_wide(c, dst=(1, "pad4")) and CS.emit_wide(c, ref=(4, "pad4"))
+
+
+def test_every_instantiation_is_launched():
+    """pc_chroma.hip: "24 ingest kernels, 64 emit kernels".  The tuples the table reaches are exactly those; a case taken away shows
+    here by the names of the kernels nothing launches any more"""
+    src = open(os.path.join(DIR, "pc_chroma.hip")).read()
+    assert "24 ingest kernels, 64 emit kernels" in src
+    assert len(CS.ALL_INGEST) == 24 and len(CS.ALL_EMIT) == 64
+    ingest, emit = CS.reached(CS.table())
+    assert ingest == CS.ALL_INGEST, "never launched: %s" % names(CS.ALL_INGEST - ingest)
+    assert emit == CS.ALL_EMIT, "never launched: %s" % names(CS.ALL_EMIT - emit)
+    # what the loops reached before the table: every ingest kernel, and all but 13 of the emit kernels -- the narrow emit without
+    # a reference ran for nv16, p210 and i444 alone
+    ingest0, emit0 = CS.reached(old_cases())
+    missing = CS.ALL_EMIT - emit0
+    print("not launched by the loops:", names(missing))
+    assert ingest0 == CS.ALL_INGEST and len(emit0) == 51 and len(missing) == 13
+    assert all(not t[5] and not t[6] for t in missing) and sum(t[3] == 2 for t in missing) == 8
+    assert {t for t in CS.ALL_EMIT if not t[5] and not t[6]} - missing == {(1, True, 2, 1, False, False, False), (2, True, 2, 1, False, False, False),
+                                                                         (1, False, 1, 1, False, False, False)}
+    # the ledger notices a case that leaves
+    table = CS.table()
+    less = [c for c in table if not (c.fmt == "i010" and c.siting == "topleft" and c.emits == ((True, False),))]
+    assert CS.ALL_EMIT - CS.reached(less)[1] == {(2, False, 2, 2, True, False, False)}
+    assert names([(2, False, 2, 2, True, False, False)]) == ["u16 planar 2:2 vco narrow image"]
+
+
+def test_the_unnamed_10_bit_words():
+    chroma, _ = _lib()
+    named = {(f.layout, f.bits, f.shift) for f in chroma.FORMATS.values()}
+    for fmt, shift in CS.UNNAMED:
+        f = chroma.FORMATS[fmt]
+        assert f.bits == 10 and shift in (0, 6) and (f.layout, 10, shift) not in named and (f.layout, 10, 6 - shift) in named
+        fr = CC.random_frame(1, 5, 7, fmt, seed=1)
+        noise = np.arange(1, 2 ** 16, 257, dtype=np.uint16)
+        w = CS.reshifted(fr, fmt, shift, noise)
+        assert all(((a >> shift) & 1023 == c).all() for a, c in zip(w, [p >> f.shift & 1023 for p in fr]))
+        assert any((a & ~np.uint16(1023 << shift)).any() for a in w)
+        assert same_frames(tuple(a & np.uint16(1023 << shift) for a in w), CS.reshifted(fr, fmt, shift))
+    assert len({(chroma.FORMATS[fmt].layout, chroma.FORMATS[fmt].sx, chroma.FORMATS[fmt].sy) for fmt, _ in CS.UNNAMED}) == 6
+
+
+def test_whole_pictures_have_the_partials_and_the_sums_the_cases_are_there_for():
+    _, L = _lib()
+    H, W, B = CS.WHOLE["H"], CS.WHOLE["W"], CS.WHOLE["B"]
+    hp, wp, top, left = K.geometry(H, W)
+    assert (hp, wp) == (1088, 1088) and hp * -(-wp // 8) == 578 * 256
+    assert {CC.sub(f) for f, _ in CS.WHOLE_FORMATS} == {(2, 2), (2, 1)} and all(s != "centre" for _, s in CS.WHOLE_FORMATS)
+    for b in (B, 3):
+        assert L.pc_chroma_emit_workspace_size(b, H, W, 2) == 24 * 259 * b and L.pc_chroma_emit_workspace_size(b, H, W, 1) == 24 * 518 * b
+    # the last chroma row's items are exactly the last block at 4:2:0, and lie in the last two blocks at 4:2:2
+    G = -(-W // 8)
+    assert (513 * G - G) // 256 == 258 and (513 * G - G) % 256 == 0 and (1026 * G - G) // 256 == 516 and -(-1026 * G // 256) == 518
+    for fmt, siting in CS.WHOLE_FORMATS:
+        x, zeros, closed = CS.whole_saturated(fmt, 64, 64)
+        small = x[:, :, :4, :8]
+        codes = CC.emit_codes(small, 0, 0, 4, 8, fmt, "bt709", "full", siting)
+        t = 2 ** CC.bits(fmt) - 1
+        assert [int(codes[p][p].min()) for p in range(3)] == [t, t, t] == [int(codes[p][p].max()) for p in range(3)]
+        Hc, Wc = CC.chroma_size(H, W, fmt)
+        assert closed == [t * t * H * W, t * t * Hc * Wc, t * t * Hc * Wc] and min(closed) > 2 ** 32
+    x, zeros, closed = CS.whole_saturated("i420", hp, wp)
+    assert closed == [68717119500, 17179279875, 17179279875]
+    got = CC.sums(x, top, left, H, W, "i420", "bt709", "full", "left", zeros)
+    assert [got[p][p] for p in range(3)] == closed
+
+
+@pytest.mark.parametrize("fmt,siting", CS.WHOLE_FORMATS)
+def test_whole_picture_tail_differs_in_the_last_rows_alone(fmt, siting):
+    H, W, B = CS.WHOLE["H"], CS.WHOLE["W"], CS.WHOLE["B"]
+    hp, wp, top, left = K.geometry(H, W)
+    left = left // 4 * 4
+    x, ref = CS.whole_tail(fmt, siting, "bt601", "limited", hp, wp, top, left)
+    got, want = CC.emit_codes(x, top, left, H, W, fmt, "bt601", "limited", siting), CC.codes(ref, fmt)
+    for p in range(3):
+        assert (got[p][:, :-1] == want[p][:, :-1]).all() and (got[p][0] == want[p][0]).all()    # every sum over the rows above is zero
+    sums = CC.sums(x, top, left, H, W, fmt, "bt601", "limited", siting, ref)
+    assert sums[0] == [0, 0, 0] and all(v > 0 for v in sums[1])

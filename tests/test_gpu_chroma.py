@@ -1,7 +1,9 @@
 """The chroma layer on the GPU (progressivecodec_amd/chroma.py, libpc_chroma.so) against its restatement
 (tests/chroma_contract.py): ingest and emit bit for bit and the sums exactly for all twelve formats, three sitings and both upsamplers
-on both access paths; against `frames` on the device where the two must agree; the halo pixels of the co-sited emit filter; sums past
-2^32 in the chroma planes; and encode_frame / decode_frame through the codec and the PCH1 container.
+on both access paths, the cases read from tests/chroma_cases.py, whose ledger says which of the 24 + 64 kernels each launches;
+against `frames` on the device where the two must agree; the halo pixels of the co-sited emit filter; sums past 2^32 in the chroma
+planes; the 10-bit words Python does not name; whole 1026 x 1030 pictures of the subsampled formats under co-sited chroma; and
+encode_frame / decode_frame through the codec and the PCH1 container.
 
 Sizes: the smallest that take every branch -- a single sample, odd dimensions, partial last items, an odd last row, more than one
 block.  Every plane is a view into a larger poisoned allocation (tests/test_gpu_frames.View), so that an element left unwritten, or
@@ -13,8 +15,10 @@ import numpy as np
 import pytest
 import torch
 
+from tests import chroma_cases as CS
 from tests import chroma_contract as CC
 from tests import frames_contract as FC
+from tests import pixels_contract as K
 from tests.test_gpu_frames import POISON64, View, check_sums, float_planes, same_bits
 from tests.util import gpu_codec
 
@@ -22,7 +26,6 @@ pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
 POL = "point-based-std"
-SIZES = [(1, 1), (2, 3), (3, 2), (37, 53), (64, 64), (67, 130)]
 
 
 def CH():
@@ -52,12 +55,13 @@ def struct_of(views):
     return CH()._frame_struct([v.t for v in views])
 
 
-def ingest_raw(views, fmt, matrix, rng, up, siting, B, H, W, Hp, Wp, top, left, dst_offset=0):
+def ingest_raw(views, fmt, matrix, rng, up, siting, B, H, W, Hp, Wp, top, left, dst_offset=0, shift=None):
     """pc_chroma_ingest into a NaN-poisoned buffer with guard floats on both sides -> (status, wide as pc_chroma_plan reports it,
-    the [B,3,Hp,Wp] result, whether the guards kept their bits)"""
+    the [B,3,Hp,Wp] result, whether the guards kept their bits).  shift: instead of the named format's"""
     ch = CH()
     L = ch.lib()
     k, f, (hs, vs) = ch.coefficients(matrix), ch.FORMATS[fmt], ch.SITINGS[siting]
+    f = f if shift is None else f._replace(shift=shift)
     n = B * 3 * Hp * Wp
     buf = torch.full((4 + dst_offset + n + 4,), float("nan"), dtype=torch.float32, device=DEV)
     dst = buf[4 + dst_offset:4 + dst_offset + n].view(B, 3, Hp, Wp)
@@ -71,12 +75,13 @@ def ingest_raw(views, fmt, matrix, rng, up, siting, B, H, W, Hp, Wp, top, left, 
     return rc, wide.value, h[4 + dst_offset:4 + dst_offset + n].reshape(B, 3, Hp, Wp), guards
 
 
-def emit_raw(xv, fmt, matrix, rng, siting, H, W, Hp, Wp, top, left, dst_views, ref_views):
+def emit_raw(xv, fmt, matrix, rng, siting, H, W, Hp, Wp, top, left, dst_views, ref_views, shift=None):
     """pc_chroma_emit -> (status, wide, the [B+2,3] sums buffer whose rows 1 .. B are `sse`, poisoned beforehand, the workspace, the
-    bytes of workspace the library asked for)"""
+    bytes of workspace the library asked for).  shift: instead of the named format's"""
     ch = CH()
     L = ch.lib()
     k, f, (hs, vs) = ch.coefficients(matrix), ch.FORMATS[fmt], ch.SITINGS[siting]
+    f = f if shift is None else f._replace(shift=shift)
     B = xv.shape[0]
     dst = struct_of(dst_views) if dst_views is not None else None
     ref = struct_of(ref_views) if ref_views is not None else None
@@ -116,30 +121,34 @@ def check_planes(dstv, want, case):
 
 # -- the full matrix -----------------------------------------------------------------------------------------------------------------
 
-def run_matrix(fmt, matrix, rng, sizes):
-    """every siting x size at batch 2: the ingest under both upsamplers, the emit with image and sums, from views that alternate
-    between loose, offset planes with an odd left (narrow) and aligned planes with left a multiple of 8 (wide)"""
+def run_matrix(cases):
+    """the cases of tests/chroma_cases.py at batch 2: the ingest under the case's upsamplers, the emit calls it lists, from views
+    that alternate between loose, offset planes with an odd left (narrow) and aligned planes with left a multiple of 8 (wide);
+    pc_chroma_plan reports the path the table predicts for every call"""
     L = CH().lib()
     seen = set()
-    for n, (siting, (H, W)) in enumerate(itertools.product(CC.SITINGS, sizes)):
+    for c in cases:
+        fmt, matrix, rng, siting, H, W, n, left, offset, mode, variant = c[:11]
         g = geometry(H, W)
+        assert (g.Hp, g.Wp, g.top, g.left) == K.geometry(H, W)
         narrow = n % 2 == 0
-        left, offset, mode, variant = (g.left, 1 + n % 3, "loose", "odd") if narrow else (g.left // 8 * 8, 0, "pad4", ("contiguous", "loose4")[n % 4 // 2])
         f = CC.random_frame(2, H, W, fmt, seed=1000 * H + W + n, garbage=True)
         case = (fmt, matrix, rng, siting, H, W, left, mode)
         views = frame_views(fmt, 2, H, W, offset, mode, f)
-        for up in CC.UPSAMPLES:
-            rc, wide, got, guards = ingest_raw(views, fmt, matrix, rng, up, siting, 2, H, W, g.Hp, g.Wp, g.top, left, dst_offset=int(narrow))
-            assert rc == 0 and guards and wide == int(not narrow), case
+        assert [v.strides[:2] for v in views] == [CS.view_strides(*rn, mode) for rn in CS.plane_rows(fmt, H, W)]
+        for up in c.ups:
+            rc, wide, got, guards = ingest_raw(views, fmt, matrix, rng, up, siting, 2, H, W, g.Hp, g.Wp, g.top, left, dst_offset=c.dst_offset)
+            assert rc == 0 and guards and wide == int(not narrow) == int(CS.ingest_wide(c)), case
             assert same_bits(got, CC.ingest(f, fmt, matrix, rng, up, siting, g.Hp, g.Wp, g.top, left)), (case, up)
         x = hostile(f, fmt, matrix, rng, siting, g.Hp, g.Wp, g.top, left, H, W, seed=n)
         xv = float_planes(x, variant)
+        assert (xv.stride(0), xv.stride(1), xv.stride(2)) == CS.float_strides(g.Hp, g.Wp, variant)[1]
         want = CC.emit(x, g.top, left, H, W, fmt, matrix, rng, siting)
         want_sums = CC.sums(x, g.top, left, H, W, fmt, matrix, rng, siting, f)
-        for with_image, with_ref in [(True, True)] + ([(False, True), (True, False)] if (H, W) == (37, 53) else []):
+        for with_image, with_ref in c.emits:
             dstv = frame_views(fmt, 2, H, W, offset, mode) if with_image else None
             rc, wide, sse, ws, need = emit_raw(xv, fmt, matrix, rng, siting, H, W, g.Hp, g.Wp, g.top, left, dstv, views if with_ref else None)
-            assert rc == 0 and wide == int(not narrow), case
+            assert rc == 0 and wide == int(not narrow) == int(CS.emit_wide(c)), case
             seen.add(wide)
             if with_ref:
                 assert need == L.pc_chroma_emit_workspace_size(2, H, W, CC.sub(fmt)[1]) > 0
@@ -153,13 +162,12 @@ def run_matrix(fmt, matrix, rng, sizes):
 
 @pytest.mark.parametrize("fmt", sorted(CC.FORMATS))
 def test_every_format_siting_and_upsampler_is_the_restatement_exactly(fmt):
-    run_matrix(fmt, "bt709", "limited", SIZES)
+    run_matrix(CS.every_format_cases(fmt))
 
 
-@pytest.mark.parametrize("fmt", ["nv16", "p210", "i444"])
+@pytest.mark.parametrize("fmt", CS.OTHER_FORMATS)
 def test_the_other_matrices_and_full_range(fmt):
-    for matrix, rng in [("bt601", "full"), ("bt2020", "limited"), ("bt2020", "full"), ("bt709", "full"), ("bt601", "limited")]:
-        run_matrix(fmt, matrix, rng, [(37, 53), (3, 2)])
+    run_matrix(CS.other_matrix_cases(fmt))
 
 
 # -- agreement with frames on the device ---------------------------------------------------------------------------------------------
@@ -322,6 +330,98 @@ def test_large_sums_and_the_last_partials_at_444():
     Y, Cb, Cr = (p.cpu().numpy() for p in (out[0], out[1][..., 0], out[1][..., 1]))
     assert (Y[0] == 1023 << 6).all() and (Cb[1] == 1023 << 6).all() and (Cr[2] == 1023 << 6).all()
     assert d.psnr_y()[0] == d.psnr_cb()[1] == d.psnr_cr()[2] == 0.0
+
+
+# -- the 10-bit words Python does not name -------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("named,shift", CS.UNNAMED)
+def test_the_unnamed_10_bit_words_are_the_named_formats_shifted(named, shift):
+    """pc_chroma.h admits bits = 10 with shift 0 or 6 in either layout; Python names semi-planar with 6 and planar with 0.  The other
+    two through the C calls, both directions, both paths: the floats, the codes and the sums of the named format of the same
+    layout; the bits of a word outside the code are ignored on input and zero on output"""
+    H, W, siting = 37, 53, "left"
+    g = geometry(H, W)
+    assert {CC.FORMATS[named][2], shift} == {0, 6}
+    f = CC.random_frame(2, H, W, named, seed=shift + 1)
+    noise = np.random.default_rng(shift).integers(0, 2 ** 16, 10 ** 5).astype(np.uint16)
+    words = CS.reshifted(f, named, shift, noise)
+    assert all((w != CS.reshifted(f, named, shift)[i]).any() for i, w in enumerate(words))
+    for n in (0, 1):
+        left, offset, mode, variant, dst_offset = CS.layout_of(n, H, W)
+        views = frame_views(named, 2, H, W, offset, mode, words)
+        for up in CC.UPSAMPLES:
+            rc, wide, got, guards = ingest_raw(views, named, "bt709", "limited", up, siting, 2, H, W, g.Hp, g.Wp, g.top, left, dst_offset, shift=shift)
+            assert rc == 0 and guards and wide == n, (named, shift, n, up)
+            assert same_bits(got, CC.ingest(f, named, "bt709", "limited", up, siting, g.Hp, g.Wp, g.top, left)), (named, shift, n, up)
+        x = hostile(f, named, "bt709", "limited", siting, g.Hp, g.Wp, g.top, left, H, W, seed=n)
+        want = CS.reshifted(CC.emit(x, g.top, left, H, W, named, "bt709", "limited", siting), named, shift)
+        assert all((p & ~np.uint16(1023 << shift) == 0).all() for p in want)
+        want_sums = CC.sums(x, g.top, left, H, W, named, "bt709", "limited", siting, f)
+        dstv = frame_views(named, 2, H, W, offset, mode)
+        rc, wide, sse, ws, need = emit_raw(float_planes(x, variant), named, "bt709", "limited", siting, H, W, g.Hp, g.Wp, g.top, left, dstv, views, shift=shift)
+        assert rc == 0 and wide == n, (named, shift, n)
+        check_sums(sse, ws, want_sums, need)
+        check_planes(dstv, want, (named, shift, n))
+
+
+# -- whole pictures: more than 256 block partials per picture in the subsampled and co-sited formats ----------------------------------------
+
+WHOLE_IDS = [f"{fmt}-{siting}" for fmt, siting in CS.WHOLE_FORMATS]
+
+
+@pytest.mark.parametrize("kind", ["hostile", "saturated", "tail"])
+@pytest.mark.parametrize("fmt,siting", CS.WHOLE_FORMATS, ids=WHOLE_IDS)
+def test_whole_pictures_planes_and_sums(fmt, siting, kind):
+    """1026 x 1030: 259 block partials per picture at 4:2:0 and 518 at 4:2:2, so that thread t of emit_final takes t, t + 256 (and
+    t + 512).  Hostile data with gray pixels on the rounding halves; white, blue and red pictures in full range against a frame of
+    zeros, whose plane p of picture p is top^2 times the plane's samples, past 2^32 in chroma too; and a picture that differs from
+    its reference in the last luma row alone, so that only the last partials are non-zero.  Image and sums on the wide path into
+    poisoned views, then the sums alone on the narrow path"""
+    H, W = CS.WHOLE["H"], CS.WHOLE["W"]
+    g = geometry(H, W)
+    left = g.left // 4 * 4
+    assert (g.Hp, g.Wp) == (1088, 1088) and left % 4 == 0 and left + W <= g.Wp
+    matrix, rng = ("bt709", "full") if kind == "saturated" else ("bt601", "limited")
+    if kind == "hostile":
+        ref = CC.random_frame(CS.WHOLE["B"], H, W, fmt, seed=21, garbage=True)
+        x = hostile(ref, fmt, matrix, rng, siting, g.Hp, g.Wp, g.top, left, H, W, seed=22)
+    elif kind == "saturated":
+        x, ref, closed = CS.whole_saturated(fmt, g.Hp, g.Wp)
+    else:
+        x, ref = CS.whole_tail(fmt, siting, matrix, rng, g.Hp, g.Wp, g.top, left)
+    B = x.shape[0]
+    want = CC.emit(x, g.top, left, H, W, fmt, matrix, rng, siting)
+    want_sums = CC.sums(x, g.top, left, H, W, fmt, matrix, rng, siting, ref)
+    if kind == "saturated":
+        assert [want_sums[p][p] for p in range(3)] == closed and min(closed) > 2 ** 32
+    if kind == "tail":
+        assert want_sums[0] == [0, 0, 0] and all(v > 0 for v in want_sums[1])
+    sy = CC.sub(fmt)[1]
+    nbytes = 24 * (259 if sy == 2 else 518) * B
+    refv, dstv = frame_views(fmt, B, H, W, 0, "pad4", ref), frame_views(fmt, B, H, W, 0, "pad4")
+    rc, wide, sse, ws, need = emit_raw(float_planes(x, "contiguous"), fmt, matrix, rng, siting, H, W, g.Hp, g.Wp, g.top, left, dstv, refv)
+    assert rc == 0 and wide == 1 and need == nbytes == CH().lib().pc_chroma_emit_workspace_size(B, H, W, sy)
+    check_sums(sse, ws, want_sums, need)
+    check_planes(dstv, want, (fmt, siting, kind))
+    del dstv
+    loose = frame_views(fmt, B, H, W, 1, "loose", ref)
+    rc, wide, sse, ws, need = emit_raw(float_planes(x, "odd"), fmt, matrix, rng, siting, H, W, g.Hp, g.Wp, g.top, left, None, loose)
+    assert rc == 0 and wide == 0 and need == nbytes
+    check_sums(sse, ws, want_sums, need)                                   # image=False: the same sums
+
+
+@pytest.mark.parametrize("fmt,siting", CS.WHOLE_FORMATS, ids=WHOLE_IDS)
+def test_whole_pictures_ingest(fmt, siting):
+    """the ingest of the same frames: 578 blocks per picture at Hp = Wp = 1088; linear on the wide path, nearest on the narrow one"""
+    H, W, B = CS.WHOLE["H"], CS.WHOLE["W"], CS.WHOLE["B"]
+    g = geometry(H, W)
+    assert g.Hp * (g.Wp // 8) == 578 * 256
+    f = CC.random_frame(B, H, W, fmt, seed=21, garbage=True)
+    for up, (left, offset, mode, dst_offset) in zip(("linear", "nearest"), [(g.left // 8 * 8, 0, "pad4", 0), (g.left, 1, "loose", 1)]):
+        views = frame_views(fmt, B, H, W, offset, mode, f)
+        rc, wide, got, guards = ingest_raw(views, fmt, "bt601", "limited", up, siting, B, H, W, g.Hp, g.Wp, g.top, left, dst_offset)
+        assert rc == 0 and guards and wide == int(up == "linear"), (fmt, up)
+        assert same_bits(got, CC.ingest(f, fmt, "bt601", "limited", up, siting, g.Hp, g.Wp, g.top, left)), (fmt, up)
 
 
 # -- through the codec ---------------------------------------------------------------------------------------------------------------

@@ -3,7 +3,7 @@
 paths, against tests/clip_rate_contract.job_sse and against clip_rate.tile_distortion_jobs of the expanded job list with the tile
 repeated; and encode_clip_to_size through the codec into a PCS2 container that clip_rate's decoders read.  Every comparison is exact
 equality of integers, bits or bytes.  T = 64 throughout (one case at 128, one at 576): the smallest tile, so that the frames stay small
-while every branch is taken."""
+while every branch is taken; the largest tiles, the later trips of the final and the long runs are in tests/test_gpu_image_limits.py."""
 import ctypes as C
 import functools
 from fractions import Fraction

@@ -1,7 +1,8 @@
 """The image-side libraries on the GPU past T = 128 (tests/image_limits.py holds the table; DESIGN.md section 19.1 the limits): the
 largest tile each library admits per format with every weight meeting the largest error; the second and the fourth trip of every
 final reduction on hostile data, and tail-only data whose only non-zero partials are the last of their row; whole pictures with more
-than 256 block partials and sums past 2^32; and the cuts at T = 576 and T = 2048.  Every comparison is exact equality of integers,
+than 256 block partials and sums past 2^32; the cuts at T = 576 and T = 2048; and clip_tol_rate's largest tiles, the trips of its
+final over an entry's wave partials, and runs longer than a wave has lanes.  Every comparison is exact equality of integers,
 bits or bytes against the restatements (tests/*_contract.py) -- for saturated inputs against the closed forms that
 tests/test_image_limits_host.py holds to the restatements; the one float64 sum is held to test_gpu_pixels.py's bound.  A case codes
 one tile, or a few, of its grid (first_tile / rect / the job list), so that none holds more than about 0.25 GB on the device."""
@@ -13,6 +14,7 @@ import torch
 
 from tests import clip_rate_contract as RC2
 from tests import clip_tol_contract as TOL
+from tests import clip_tol_rate_contract as TRC
 from tests import clips_contract as CC
 from tests import frame_rate_contract as QC
 from tests import frame_tiles_contract as GC
@@ -24,6 +26,7 @@ from tests import tiles_contract as TC
 from tests.test_gpu_clip_rate import jobs_raw
 from tests.test_gpu_clip_tol import check as check_scan
 from tests.test_gpu_clip_tol import clip_codes, scan_raw
+from tests.test_gpu_clip_tol_rate import runs_raw
 from tests.test_gpu_clips import changes_raw, frame_pair, views
 from tests.test_gpu_frame_rate import ref_views
 from tests.test_gpu_frame_rate import sse_raw as frame_sse_raw
@@ -45,9 +48,9 @@ def need_memory(nbytes):
 
 
 def mods():
-    from progressivecodec_amd import clip_rate, clip_tol, clips, frame_rate, frame_tiles, frames, pixels, rate, tiles
+    from progressivecodec_amd import clip_rate, clip_tol, clip_tol_rate, clips, frame_rate, frame_tiles, frames, pixels, rate, tiles
     return dict(rate=rate, frame_rate=frame_rate, clip_rate=clip_rate, clips=clips, clip_tol=clip_tol, pixels=pixels, frames=frames,
-                tiles=tiles, frame_tiles=frame_tiles)
+                tiles=tiles, frame_tiles=frame_tiles, clip_tol_rate=clip_tol_rate)
 
 
 def planes_of(f):
@@ -623,3 +626,122 @@ def test_frame_cuts_at_2048():
         assert same_bits(x, want)
         del x
         assert same_bits(cl.cut_tiles(planes, "p010", [4], "bt709", "limited", "linear", T, O), want)
+
+
+# -- E: clip_tol_rate: the largest tile, the later trips of its final over an entry's wave partials, long runs ------------------------------
+
+def expanded_rows(x, g, planes, tile_ids, runs, fmt, matrix, rng):
+    """clip_rate.tile_distortion_jobs of the expanded job list, a job's entries at a time (at T = 2048 a tile is 50 MB)"""
+    cr = mods()["clip_rate"]
+    out = []
+    for m, (t, run) in enumerate(zip(tile_ids, runs)):
+        for a in range(0, len(run), 64):
+            part = run[a:a + 64]
+            rep = x[m:m + 1].expand(len(part), -1, -1, -1).contiguous()
+            out += cr.tile_distortion_jobs(rep, g, planes, [(f, t) for f in part], fmt, matrix, rng).tolist()
+            del rep
+    return out
+
+
+@pytest.mark.parametrize("fmt", FC.FORMATS)
+def test_clip_tol_rate_largest_tile_runs_are_frame_rates_values(fmt):
+    """nv12 / i420 at T = 2048 (4096 wave partials per entry, 64 trips of the final), p010 at T = 1024 (1024, 16 trips), O = T / 2, full
+    range: zero and one tiles against both saturated frames, a frame twice in a run, a corner tile; every row is the closed form of
+    its (tile value, frame) pair and clip_rate's value of the expanded job; the next tile size is refused for the format"""
+    need_memory(500 << 20)
+    ctr = mods()["clip_tol_rate"]
+    c = IL.FRAME_LIMITS[fmt]
+    H, W, T, O = (c[k] for k in ("H", "W", "T", "O"))
+    clip, vals, tile_ids, runs, want = IL.run_limit_case(fmt)
+    x_np = np.concatenate([IL.const_tile(T, v) for v in vals])
+    for modes, variant in [(ALIGNED, "contiguous"), (MIXED, "odd")]:
+        x = float_tiles(x_np, variant, T)
+        table = table_of(fmt, H, W, modes, clip)
+        assert ctr.plan(x, table, fmt, overlap=O) is (variant == "contiguous")
+        rc, buf, ws_ok = runs_raw(x, H, W, O, fmt, "full", "bt709", table, tile_ids, runs, T)
+        assert rc == 0 and ws_ok, (fmt, variant)
+        check_out(buf, want, (fmt, variant))
+        if variant == "contiguous":
+            frames = [tuple(p[0] for p in ts) for ts in table]
+            g = ctr.grid_of(H, W, T, O)
+            got, off = ctr.tile_distortion_runs(x, g, frames, tile_ids, runs, fmt, "bt709", "full")
+            assert got.dtype == torch.int64 and got.tolist() == want and off == [0, 3, 5, 6]          # 58 bits reach Python
+            assert expanded_rows(x, g, frames, tile_ids, runs, fmt, "bt709", "full") == want
+        del x, table
+    big = T + 64
+    x = torch.zeros((1, 3, big, big), device=DEV)
+    rc, buf, ws_ok = runs_raw(x, H, W, 0, fmt, "full", "bt709", table_of(fmt, H, W, ALIGNED, clip), [0], [[0]], big)
+    torch.cuda.synchronize()
+    assert rc == -1 and ws_ok and (buf == -0x5A5A5A5A5A5A5A5B).all()
+
+
+@pytest.mark.parametrize("case", IL.run_trip_cases(), ids=lambda c: f"T{c[0]}-O{c[3]}-{c[5]}")
+def test_clip_tol_rate_later_trips_on_hostile_data(case):
+    """T = 576: 324 wave partials per entry, six trips; T = 1024: 1024, sixteen; tile 3 of the latter is clipped to 6 x 476, so that
+    most of its blocks hold no active item and still write their zeros"""
+    T, H, W, O, wide, fmt = case
+    ctr = mods()["clip_tol_rate"]
+    ny, nx = TC.grid(H, W, T, O)
+    tile_ids, runs = IL.run_list(ny * nx)
+    off = TRC.offsets_of(runs)
+    x_np = np.array(hostile(len(tile_ids), T, W + O))
+    clip = [FC.random_frame(1, H, W, fmt, seed=T + O + s) for s in range(2)]
+    want = TRC.run_sse(x_np, clip, tile_ids, runs, H, W, T, O, fmt, "bt2020", "full")
+    assert want[off[1]] != want[off[3]] and tile_ids[1] == tile_ids[3] and runs[1][0] != runs[3][0]
+    x = float_tiles(x_np, "contiguous" if wide else "odd", T)
+    table = table_of(fmt, H, W, ALIGNED if wide else MIXED, clip)
+    assert ctr.plan(x, table, fmt, overlap=O) is wide
+    rc, buf, ws_ok = runs_raw(x, H, W, O, fmt, "full", "bt2020", table, tile_ids, runs, T)
+    assert rc == 0 and ws_ok
+    check_out(buf, want, case)
+    rc, buf, ws_ok = runs_raw(x[1:3], H, W, O, fmt, "full", "bt2020", table, tile_ids[1:3], runs[1:3], T)
+    assert rc == 0 and ws_ok
+    check_out(buf, want[off[1]:off[3]], (case, "sub-list"))
+    frames = [tuple(p[0] for p in ts) for ts in table]
+    assert expanded_rows(x, ctr.grid_of(H, W, T, O), frames, tile_ids, runs, fmt, "bt2020", "full") == want
+
+
+@pytest.mark.parametrize("fmt", FC.FORMATS)
+def test_clip_tol_rate_tail_only(fmt):
+    """the tail tile and the equal tile, each against the frame twice: of an entry's 324 wave partials only the last block's four
+    are non-zero, which the final's sixth trip gathers"""
+    T, H, W = (IL.SECOND_TRIP[k] for k in ("T", "H", "W"))
+    tail, eq, frame = IL.frame_tail(fmt, T, H, W)
+    row = QC.tile_sse(tail, H, W, T, 0, fmt, "bt709", "limited", frame)[0]
+    want = [row, row, [0, 0, 0], [0, 0, 0]]
+    assert all(v > 0 for v in row)
+    other = FC.random_frame(1, H, W, fmt, seed=77)
+    for variant, modes in [("contiguous", ALIGNED), ("odd", MIXED)]:
+        x = float_tiles(np.concatenate([tail, eq]), variant, T)
+        table = table_of(fmt, H, W, modes, (frame, other))
+        rc, buf, ws_ok = runs_raw(x, H, W, 0, fmt, "limited", "bt709", table, [0, 0], [[0, 0], [0, 0]], T)
+        assert rc == 0 and ws_ok
+        check_out(buf, want, (fmt, variant))
+
+
+@pytest.mark.parametrize("fmt", FC.FORMATS)
+def test_clip_tol_rate_long_runs_and_many_entries(fmt):
+    """T = 64, 100 x 150, three frames, six jobs of 70, 1, 2, 33, 64 and 130 entries: the entry loop runs past a wave's lanes, and
+    the final has 300 rows"""
+    ctr = mods()["clip_tol_rate"]
+    c = IL.LONG_RUNS
+    T, H, W, O = (c[k] for k in ("T", "H", "W", "O"))
+    tile_ids, runs = IL.long_runs()
+    off = TRC.offsets_of(runs)
+    x_np = np.array(hostile(len(tile_ids), T, 300))
+    clip = [FC.random_frame(1, H, W, fmt, seed=300 + s) for s in range(3)]
+    want = TRC.run_sse(x_np, clip, tile_ids, runs, H, W, T, O, fmt, "bt601", "limited")
+    assert len(want) == 300 and all(any(want[off[m] + j] != want[off[m]] for j in range(64, len(runs[m]))) for m in (0, 5))
+    g = ctr.grid_of(H, W, T, O)
+    for modes, variant in [(ALIGNED, "contiguous"), (MIXED, "odd")]:
+        x = float_tiles(x_np, variant, T)
+        table = table_of(fmt, H, W, modes, clip)
+        assert ctr.plan(x, table, fmt, overlap=O) is (variant == "contiguous")
+        rc, buf, ws_ok = runs_raw(x, H, W, O, fmt, "limited", "bt601", table, tile_ids, runs, T)
+        assert rc == 0 and ws_ok, (fmt, variant)
+        check_out(buf, want, (fmt, variant))
+        frames = [tuple(p[0] for p in ts) for ts in table]
+        got, goff = ctr.tile_distortion_runs(x, g, frames, tile_ids, runs, fmt, "bt601", "limited")
+        assert got.shape == (300, 3) and got.tolist() == want and goff == off
+        if variant == "contiguous":
+            assert expanded_rows(x, g, frames, tile_ids, runs, fmt, "bt601", "limited") == want

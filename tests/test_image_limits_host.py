@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from tests import clip_tol_contract as TOL
+from tests import clip_tol_rate_contract as TRC
 from tests import clips_contract as CC
 from tests import frame_rate_contract as QC
 from tests import frame_tiles_contract as GC
@@ -17,20 +18,24 @@ from tests import tiles_contract as TC
 
 
 def libs():
-    from progressivecodec_amd import clip_rate, clip_tol, clips, frame_rate, rate
+    from progressivecodec_amd import clip_rate, clip_tol, clip_tol_rate, clips, frame_rate, rate
     return {"rate": rate.lib().pc_rate_workspace_size, "frame_rate": frame_rate.lib().pc_frame_rate_workspace_size,
             "clip_rate": clip_rate.lib().pc_clip_rate_workspace_size, "clips": clips.lib().pc_clips_changes_workspace_size,
-            "clip_tol": clip_tol.lib().pc_clip_tol_workspace_size}
+            "clip_tol": clip_tol.lib().pc_clip_tol_workspace_size, "clip_tol_rate": clip_tol_rate.lib().pc_clip_tol_rate_workspace_size}
 
 
 def partials_per_tile(name, T):
     """the block partials of one tile's row, the halo block of the clip libraries included: the workspace of one tile over the bytes
-    of one partial (clip_tol's also holds the tile's 4-byte anchor, rounded up to 8)"""
+    of one partial (clip_tol's also holds the tile's 4-byte anchor, rounded up to 8).  clip_tol_rate writes a partial per wave, four
+    to a block, and its row is an entry's: the figure here is the blocks, as for the others"""
     nbytes = libs()[name](T, 1)
     assert nbytes > 0
     if name == "clip_tol":
         assert (nbytes - 8) % 72 == 0 and nbytes == TOL.workspace_size(T, 1)
         return (nbytes - 8) // 72
+    if name == "clip_tol_rate":
+        assert nbytes % 96 == 0
+        return nbytes // 96
     assert nbytes % 24 == 0
     return nbytes // 24
 
@@ -204,3 +209,77 @@ def test_whole_picture_tail_pairs_are_non_zero_through_the_last_two_rows_alone()
     assert not (TC.stitch(xt, H, W, T, O, "nearest", "chw")[:, :H - 2] != img[:, :H - 2]).any()
     fr = GC.stitch(xe, H, W, T, O, "p010", "bt709", "limited")
     assert all(v > 0 for v in GC.sums(xt, H, W, T, O, "p010", "bt709", "limited", fr)) and GC.sums(xe, H, W, T, O, "p010", "bt709", "limited", fr) == [0, 0, 0]
+
+
+# -- clip_tol_rate ---------------------------------------------------------------------------------------------------------------------
+
+def test_clip_tol_rate_limits_and_the_trips_of_its_final():
+    """the per-format limit is the module's and the restatement's; an entry's row of WAVE partials is 4096 long at T = 2048 (64 trips
+    of the final's 64 lanes), 1024 at T = 1024 (16), 324 at T = 576 (six, the last partial); and the workspace of every case of the
+    table is 96 (T^2 / 4096) n_entries"""
+    from progressivecodec_amd import clip_tol_rate
+    size = libs()["clip_tol_rate"]
+    for fmt, c in IL.FRAME_LIMITS.items():
+        assert c["T"] == IL.T_MAX["clip_tol_rate"][FC.bits(fmt)] == QC.max_tile(fmt) == clip_tol_rate.max_tile(fmt)
+    waves = lambda T: size(T, 1) // 24                                                     # noqa: E731
+    assert (waves(2048), waves(1024), waves(576), waves(64)) == (4096, 1024, 324, 4)
+    assert (-(-waves(2048) // 64), -(-waves(1024) // 64), -(-waves(576) // 64)) == (64, 16, 6) and waves(576) % 64 == 4
+    cases = IL.run_workspace_cases()
+    assert len(cases) == 3 + 10 + 2 and (64, 300) in cases
+    for T, ne in cases:
+        assert size(T, ne) == 96 * (T * T // 4096) * ne == TRC.workspace_size(T, ne), (T, ne)
+    assert max(size(T, ne) for T, ne in cases) < 1 << 20
+
+
+@pytest.mark.parametrize("fmt", FC.FORMATS)
+def test_clip_tol_rate_closed_forms_are_the_restatement(fmt):
+    """A: every row of the three jobs is frame_rate_closed of its (tile value, frame) pair and run_sse's row; the jobs reach both
+    frames from both tile values, a frame twice in one run and the corner tile"""
+    c = IL.FRAME_LIMITS[fmt]
+    frames, vals, tile_ids, runs, want = IL.run_limit_case(fmt)
+    x = np.concatenate([IL.const_tile(c["T"], v) for v in vals])
+    assert TRC.run_sse(x, frames, tile_ids, runs, c["H"], c["W"], c["T"], c["O"], fmt, "bt709", "full") == want
+    assert len(want) == 6 and want[0] == want[2] != want[1] and want[5] != want[0]
+    for (v, mirror), closed in {(0.0, False): want[0], (1.0, True): want[3]}.items():            # the pairs frame_rate's case has
+        _, _, eY, eC = IL.frame_saturated(fmt, mirror)
+        assert IL.saturated_errors(fmt, v, mirror) == (eY, eC) and closed == IL.frame_rate_closed(c, eY, eC)
+    # the other two pairs leave luma equal: the whole sum is chroma's
+    assert want[1][0] == want[4][0] == 0 and min(want[1][1:] + want[4][1:]) >= 2 ** 53
+    assert all(s < 2 ** 60 for row in want for s in row) and max(want[0]) >= 2 ** 54
+    assert all((a == b).all() for a, b in zip(frames[0], frames[2])) and any((a != b).any() for a, b in zip(frames[0], frames[1]))
+
+
+def test_clip_tol_rate_run_lists_are_what_the_cases_need():
+    for n in (4, 6):
+        tile_ids, runs = IL.run_list(n)
+        assert {s for r in runs for s in r} == {0, 1} and any(len(set(r)) < len(r) for r in runs) and runs[0][0] > runs[0][1]
+        assert tile_ids[1] == tile_ids[3] and runs[1] != runs[3] and {0, n - 1} <= set(tile_ids)
+    cases = IL.run_trip_cases()
+    assert len(cases) == 10 and {(c[3], c[5]) for c in cases[:9]} == {(O, f) for O, _ in IL.SECOND_TRIP_OVERLAPS for f in FC.FORMATS}
+    assert cases[-1] == (1024, 1030, 1500, 0, True, "p010") and 3 in IL.run_list(4)[0]          # tile 3, clipped to 6 x 476
+    c = IL.LONG_RUNS
+    tile_ids, runs = IL.long_runs()
+    assert TC.grid(c["H"], c["W"], c["T"], c["O"]) == (2, 3) and c["O"] % 8 == 0 and all(0 <= t < 6 for t in tile_ids)
+    assert [len(r) for r in runs] == [70, 1, 2, 33, 64, 130] and TRC.offsets_of(runs)[-1] == 300 and len(tile_ids) == 6
+    for r in runs:
+        assert set(r) <= {0, 1, 2} and (len(r) < 3 or set(r) == {0, 1, 2})
+        assert len(r) < 5 or any(a == b for a, b in zip(r, r[1:]))                              # a frame twice in a row
+    # past the 64th entry a run names other frames than at its start: a loop that ran out of entries of its own would show
+    assert all(any(r[j] != r[0] for j in range(64, len(r))) for r in runs if len(r) > 64) and sum(len(r) > 64 for r in runs) == 2
+
+
+@pytest.mark.parametrize("fmt", FC.FORMATS)
+def test_clip_tol_rate_tail_only_comes_from_the_last_row_pair_alone(fmt):
+    T, H, W = (IL.SECOND_TRIP[k] for k in ("T", "H", "W"))
+    tail, eq, frame = IL.frame_tail(fmt, T, H, W)
+    assert np.array_equal(tail[:, :, :T - 2].view(np.uint32), eq[:, :, :T - 2].view(np.uint32))
+    x = np.concatenate([tail, eq])
+    got = TRC.run_sse(x, [frame], [0, 0], [[0, 0], [0, 0]], H, W, T, 0, fmt, "bt709", "limited")
+    want = QC.tile_sse(tail, H, W, T, 0, fmt, "bt709", "limited", frame)[0]
+    assert got == [want, want, [0, 0, 0], [0, 0, 0]] and all(v > 0 for v in want)
+    # the same value from the last row pair on its own: the tile of T rows whose first T - 2 are the equal tile's, so that every
+    # item above the last row pair adds nothing -- of an entry's 324 wave partials only the last block's are non-zero
+    y, cb, cr = QC.tile_codes(tail[0], T, T, fmt, "bt709", "limited")
+    ey, ecb, ecr = QC.tile_codes(eq[0], T, T, fmt, "bt709", "limited")
+    assert (y[:T - 2] == ey[:T - 2]).all() and (cb[:T // 2 - 1] == ecb[:T // 2 - 1]).all() and (cr[:T // 2 - 1] == ecr[:T // 2 - 1]).all()
+    assert want == [int(((y[T - 2:] - ey[T - 2:]) ** 2).sum()), int(((cb[-1] - ecb[-1]) ** 2).sum()), int(((cr[-1] - ecr[-1]) ** 2).sum())]
