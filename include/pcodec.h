@@ -191,6 +191,9 @@ PC_API int pc_codec_set_threads(pc_codec* c, int n_threads);
  *   "host_threads"            as pc_codec_set_threads
  *   "profile_in_schedule" 0/1 1: pc_codec_profile_begin only brackets the launches and leaves the schedule alone (default 0: profiling
  *                             forces the serial schedule so that a launch's duration is its own)
+ *   "group_siblings" 0 / 1    1 (default): sibling convolutions of identical shape share launches -- layer 1 of the hyper-synthesis nets
+ *                             as one wide layer, their layers 2-5 as scale || mean pairs, and unit k of the two branches of a
+ *                             window-attention module at small M as one grouped unit; 0: one launch per layer (for A/B timing)
  * Unknown names and out-of-range values return PC_ERR_ARG.  The conv kernel's tuning switches (PC_CONV_*) exist only in the -DPC_TUNING
  * build of the library (csrc/Makefile `tuning`), not here. */
 PC_API int pc_codec_set_option(pc_codec* c, const char* name, int value);
@@ -410,6 +413,9 @@ typedef struct pc_test_conv_desc {
 #define PC_FORM_L0_GENERIC 6               /* layout-0 kernel: generic epilogue */
 #define PC_FORM_IN_GDN 7                   /* fused input-layer GDN */
 PC_API int pc_test_conv(const pc_test_conv_desc* d, int* plan, void* stream);
+/* pc_test_conv of a grouped launch (ngroup == 2) whose second GEMM reads an aux0 tensor of its own, g1_aux0, with the pixel stride ld0 of
+ * the descriptor (the two branches' ResidualUnit tails of a window-attention module); NULL: pc_test_conv. */
+PC_API int pc_test_conv_g1aux(const pc_test_conv_desc* d, const float* g1_aux0, int* plan, void* stream);
 
 /* Test aid: one launch of a non-conv stage launcher (progressivecodec_amd/csrc/pc_stages.hip; GDN: the codec's own gdn()) from a plain
  * descriptor that carries the union of the launchers' arguments, the ones the wrappers above hide included (lik / lik_sb, mask_src /

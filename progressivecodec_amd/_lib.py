@@ -24,7 +24,7 @@ EXPORTS = [
     "pc_codec_host_stats", "pc_codec_set_rem_checkpoint", "pc_codec_set_option", "pc_selftest_packed_gelu", "pc_profile_set_epoch", "pc_codec_profile_intervals",
     "pc_codec_set_post_filter", "pc_codec_post_filter",
     "pc_codec_set_model", "pc_codec_wacnn_compress", "pc_codec_wacnn_decompress", "pc_codec_wacnn_forward",
-    "pc_test_conv", "pc_codec_set_topology", "pc_test_stage",
+    "pc_test_conv", "pc_codec_set_topology", "pc_test_stage", "pc_test_conv_g1aux",
 ]
 
 
@@ -84,6 +84,8 @@ def lib():
             L.pc_selftest_packed_gelu.argtypes = [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         if hasattr(L, "pc_test_conv"):
             L.pc_test_conv.argtypes = [vp, C.POINTER(C.c_int), vp]      # (pc_test_conv_desc*: tests/conv_contract.py mirrors the struct)
+        if hasattr(L, "pc_test_conv_g1aux"):
+            L.pc_test_conv_g1aux.argtypes = [vp, vp, C.POINTER(C.c_int), vp]
         if hasattr(L, "pc_test_stage"):
             L.pc_test_stage.argtypes = [vp, C.POINTER(C.c_int), vp]     # (pc_test_stage_desc*: tests/stage_contract.py mirrors the struct)
         L.pc_codec_compress.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, vp, vp]

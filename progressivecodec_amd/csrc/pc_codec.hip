@@ -108,6 +108,9 @@ struct pc_codec {
     const float* cust_map = nullptr;             // pc_codec_set_cust_map: consumed by the next compress / decompress call
     const float* rem_ckpt = nullptr;             // pc_codec_set_rem_checkpoint: NCHW [B][320][HW] representation for the REM nets' x_base input (next call)
     int opt_serial = 0, opt_lanes_enc = 0, opt_lanes_dec = 0;   // pc_codec_set_option
+    int opt_group_siblings = (int)pc_tune("PC_GROUP_SIBLINGS", 1);   // pc_codec_set_option: sibling convolutions share launches (hyper(), wam())
+    ConvW hs_c0_cat2, hs_c0_cat4;                // layer 1 of the hyper-synthesis nets that run together, output channels side by side:
+                                                 // scale, mean of the base (2) and of the enhancement behind them (4); load_hs_cat
     int rem_mu_std = 0;                          // the loaded post_latent nets are the mu_std=True form (2N-channel enhancement branch and output)
     float* eb_net = nullptr;                     // [192][PC_EB_NET_FLOATS] device: density network of the EntropyBottleneck (forward path)
     float* scale_table = nullptr;                // [64] device
@@ -198,7 +201,7 @@ int launch_conv(const pc_conv_params& q_in, hipStream_t st, int* plan = nullptr)
     by += ng * 4.0 * ((double)taps * q.Cin * q.Cout + q.Cout);
     if (q.fg_gamma) by += 4.0 * ((double)q.Cout * q.Cout + q.Cout);
     by += ng * 4.0 * (double)q.nphase * q.M * q.Cout;
-    if (q.aux0 && q.epi != PC_EPI_NONE && q.epi != PC_EPI_GELU && q.epi != PC_EPI_CLAMP01) by += 4.0 * (double)q.nphase * q.M * q.Cout;
+    if (q.aux0 && q.epi != PC_EPI_NONE && q.epi != PC_EPI_GELU && q.epi != PC_EPI_CLAMP01) by += (q.g1_aux0 ? ng : 1.0) * 4.0 * (double)q.nphase * q.M * q.Cout;
     if (q.aux1 && (q.epi == PC_EPI_GATE || q.epi == PC_EPI_LRP_ADD)) by += 4.0 * (double)q.nphase * q.M * q.Cout;
     hipEvent_t e0, e1;
     {
@@ -424,6 +427,28 @@ int load_hs(pc_codec* c, const std::string& p, HsW* h)
     return PC_OK;
 }
 
+// Layer 1 (3x3, 192 -> 192) of n hyper-synthesis nets as ONE layer of n * 192 outputs: the module weights [192][192][3][3] and biases
+// appended along the output channel, then packed like any conv.  Every output channel keeps its own K chain, so channel 192 j + o of
+// the wide layer is channel o of net j, bit for bit (tests/test_sibling_pack_host.py, tests/test_gpu_sibling_groups.py).
+int load_hs_cat(pc_codec* c, std::initializer_list<std::string> prefixes, ConvW* out)
+{
+    const int n = (int)prefixes.size();
+    std::vector<float> w, bias;
+    for (const std::string& p : prefixes) {
+        const HostTensor* wt = find(c, p + ".0.weight", PC_F32, {192, NCH, 3, 3});
+        const HostTensor* bt = find(c, p + ".0.bias", PC_F32, {192});
+        if (!wt || !bt) { std::fprintf(stderr, "[pcodec] missing/mis-shaped tensor %s.0\n", p.c_str()); return PC_ERR_MISSING; }
+        w.insert(w.end(), reinterpret_cast<const float*>(wt->data.data()), reinterpret_cast<const float*>(wt->data.data()) + (size_t)192 * NCH * 9);
+        bias.insert(bias.end(), reinterpret_cast<const float*>(bt->data.data()), reinterpret_cast<const float*>(bt->data.data()) + 192);
+    }
+    std::vector<float> packed(w.size());
+    PCCHK(pc_pack_conv_weight(w.data(), 0, n * 192, NCH, 3, packed.data()));
+    PCCHK(upload(c, packed, &out->w));
+    PCCHK(upload(c, bias, &out->b));
+    out->Cin = NCH; out->Cout = n * 192; out->k = 3; out->kind = 0; out->layout = pc_conv_weight_layout(0, NCH, n * 192, 3);
+    return PC_OK;
+}
+
 // ------------------------------------------------------------------------------------------ launch helpers
 struct Seg { const float* p; int ld; int nch; };
 
@@ -486,7 +511,7 @@ int conv_geometry(pc_conv_params& q, int kind, int k, int stride, int H, int W, 
 }
 
 // generic conv over NHWC segments -> NHWC output slice (channel offset folded into `out`, pixel stride ldo)
-struct Group1 { const ConvW* w; const float* seg0; float* out; };   // second GEMM of a grouped launch
+struct Group1 { const ConvW* w; const float* seg0; float* out; const float* aux0 = nullptr; };   // second GEMM of a grouped launch (aux0: its own residual tensor, pixel stride ld0)
 
 int conv_n(hipStream_t st, const ConvW& w, const Seg* segs, int nseg, int B, int H, int W, int stride,
            float* out, int ldo, int epi, const float* aux0 = nullptr, int ld0 = 0, const float* aux1 = nullptr, int ld1 = 0,
@@ -510,7 +535,7 @@ int conv_n(hipStream_t st, const ConvW& w, const Seg* segs, int nseg, int B, int
     q.out_sc = 1; q.out_sx = ldo; q.out_sy = (int64_t)q.outW * ldo; q.out_sb = (int64_t)q.outH * q.outW * ldo;
     if (g1) {
         if (g1->w->Cin != w.Cin || g1->w->Cout != w.Cout || g1->w->k != w.k || g1->w->layout != 1 || w.layout != 1) return PC_ERR_ARG;
-        q.ngroup = 2; q.g1_seg0 = g1->seg0; q.g1_w = g1->w->w; q.g1_bias = g1->w->b; q.g1_out = g1->out;
+        q.ngroup = 2; q.g1_seg0 = g1->seg0; q.g1_w = g1->w->w; q.g1_bias = g1->w->b; q.g1_out = g1->out; q.g1_aux0 = g1->aux0;
     }
     return launch_conv(q, st);
 }
@@ -545,6 +570,19 @@ int ru(hipStream_t st, const RuW& r, const float* x, int C, int B, int H, int W,
     return PC_OK;
 }
 
+// two ResidualUnits of identical shape on independent inputs (unit k of a window-attention module's two branches) as three grouped launches
+int ru_pair(hipStream_t st, const RuW& ra, const RuW& rb, const float* xa, const float* xb, int C, int B, int H, int W,
+            float* ta1, float* ta2, float* tb1, float* tb2, float* outa, float* outb)
+{
+    Group1 g{&rb.c0, xb, tb1};
+    PCCHK(conv(st, ra.c0, {{xa, C, C}}, B, H, W, 1, ta1, C / 2, PC_EPI_GELU, nullptr, 0, nullptr, 0, false, &g));
+    g = Group1{&rb.c2, tb1, tb2};
+    PCCHK(conv(st, ra.c2, {{ta1, C / 2, C / 2}}, B, H, W, 1, ta2, C / 2, PC_EPI_GELU, nullptr, 0, nullptr, 0, false, &g));
+    g = Group1{&rb.c4, tb2, outb, xb};
+    PCCHK(conv(st, ra.c4, {{ta2, C / 2, C / 2}}, B, H, W, 1, outa, C, PC_EPI_RES_GELU, xa, C, nullptr, 0, false, &g));
+    return PC_OK;
+}
+
 // Win_noShift_Attention (layers/layers.py:59-75)
 int wam(pc_codec* c, hipStream_t st, const WamW& w, const float* x, int B, int H, int W, float* out, int ldo = 0)
 {
@@ -560,6 +598,22 @@ int wam(pc_codec* c, hipStream_t st, const WamW& w, const float* x, int B, int H
     PCCHK(c->buf("wam_qkv", M * 3 * C, &qkv));
     float* b1;
     PCCHK(c->buf("wam_b1", M * C, &b1));
+    // Small M (the latent-resolution modules: 1.25-2.5 rounds of 32x32 accumulator chains per launch): branch a moves
+    // behind attention + proj and unit k of the two branches -- identical shapes, no dependence on each other before the gate -- runs as
+    // three grouped launches a[k] || b[k]; the last one reads each branch's own residual (Group1::aux0).  Same chains, same bits.
+    if (c->opt_group_siblings && (long)((M + 31) / 32) * ((C / 2 + 31) / 32) < 4096 && w.a[0].c0.layout == 1 && w.a[0].c2.layout == 1 && w.a[0].c4.layout == 1) {
+        float *u1, *u2;
+        PCCHK(c->buf("wam_u1", M * (C / 2), &u1));
+        PCCHK(c->buf("wam_u2", M * (C / 2), &u2));
+        PCCHK(conv(st, w.qkv, {{x, C, C}}, B, H, W, 1, qkv, 3 * C, PC_EPI_NONE));
+        PCCHK(pc_win_attention_launch(qkv, w.bias, B, H, W, C, HEADS, w.ws, w.shift, (float)std::pow((double)(C / HEADS), -0.5), a1, st, 1));
+        PCCHK(conv(st, w.proj, {{a1, C, C}}, B, H, W, 1, o, C, PC_EPI_RES, x, C));     // shortcut + proj(attn); a1 is free again
+        PCCHK(ru_pair(st, w.a[0], w.b[0], x, o, C, B, H, W, t1, t2, u1, u2, a0, b1));
+        PCCHK(ru_pair(st, w.a[1], w.b[1], a0, b1, C, B, H, W, t1, t2, u1, u2, a1, o));
+        PCCHK(ru_pair(st, w.a[2], w.b[2], a1, o, C, B, H, W, t1, t2, u1, u2, a0, b1));   // a in a0, b in b1
+        PCCHK(conv(st, w.out, {{b1, C, C}}, B, H, W, 1, out, ldo, PC_EPI_GATE, a0, C, x, C));
+        return PC_OK;
+    }
     // branch a: three residual units
     PCCHK(ru(st, w.a[0], x, C, B, H, W, t1, t2, a0));
     PCCHK(ru(st, w.a[1], a0, C, B, H, W, t1, t2, a1));
@@ -877,6 +931,40 @@ int hyper(pc_codec* c, hipStream_t st, const float* z_hat, int B, int zh, int zw
     // (base only) or four nets side by side on streams of their own was worth 1 % in round 1; with the encoder / decoder objects side
     // by side and the chains pipelined it cost 3 % of the overlapped bench and 2-5 % of the sequential one
     // (profiles/r03_t_hyper_parallel_ab.log): four more streams' launches in a chip that is already shared by four chains.  Removed.
+    // What remains of the idea needs no stream: the nets are siblings of identical shape, and at 0.1-2.5 rounds of accumulator chains per
+    // launch one launch can carry two or four of them.  Layer 1 of every net reads z_hat: ONE launch with the nets'
+    // output channels side by side (hs_c0_cat*, packed at finalize); layers 2-5 of scale || mean as grouped launches, per level.
+    if (c->opt_group_siblings) {
+        const bool one = quality != 0 && c->topo.single_hyperprior;   // one 640-output pair: the enhancement chain reads its channels [320:]
+        const int n = (quality != 0 && !one) ? 4 : 2;                 // nets: scale, mean (base), then scale, mean (enhancement)
+        const HsW* nets[4] = {&c->hss[one ? 1 : 0], &c->hms[one ? 1 : 0], &c->hss[1], &c->hms[1]};
+        float* outs[4] = {ls, lm, ls + D0, lm + D0};
+        const ConvW& cat = n == 4 ? c->hs_c0_cat4 : c->hs_c0_cat2;
+        if (!cat.w || cat.Cout != n * 192 || cat.layout != 1) return PC_ERR_STATE;
+        const size_t M = (size_t)B * zh * zw;
+        float *t0, *t1[4], *t2[4], *t3[4];
+        PCCHK(c->buf("hs_c0", M * 4 * 192, &t0));
+        for (int j = 0; j < n; ++j) {                                  // scratch per net, all of it before the first launch
+            const std::string s = std::to_string(j);
+            PCCHK(c->buf("hs_t1_" + s, M * 4 * 224, &t1[j]));
+            PCCHK(c->buf("hs_t2_" + s, M * 4 * 256, &t2[j]));
+            PCCHK(c->buf("hs_t3_" + s, M * 16 * 288, &t3[j]));
+        }
+        const int ld = n * 192;                                        // net j's layer-1 activations: channels [192 j, 192 j + 192)
+        PCCHK(conv(st, cat, {{z_hat, 192, 192}}, B, zh, zw, 1, t0, ld, PC_EPI_GELU));
+        for (int p = 0; p < n; p += 2) {
+            const HsW &a = *nets[p], &b = *nets[p + 1];
+            Group1 g{&b.c2, t0 + 192 * (p + 1), t1[p + 1]};
+            PCCHK(conv(st, a.c2, {{t0 + 192 * p, ld, 192}}, B, zh, zw, 1, t1[p], 224, PC_EPI_GELU, nullptr, 0, nullptr, 0, true, &g));
+            g = Group1{&b.c4, t1[p + 1], t2[p + 1]};
+            PCCHK(conv(st, a.c4, {{t1[p], 224, 224}}, B, 2 * zh, 2 * zw, 1, t2[p], 256, PC_EPI_GELU, nullptr, 0, nullptr, 0, false, &g));
+            g = Group1{&b.c6, t2[p + 1], t3[p + 1]};
+            PCCHK(conv(st, a.c6, {{t2[p], 256, 256}}, B, 2 * zh, 2 * zw, 1, t3[p], 288, PC_EPI_GELU, nullptr, 0, nullptr, 0, true, &g));
+            g = Group1{&b.c8, t3[p + 1], outs[p + 1]};
+            PCCHK(conv(st, a.c8, {{t3[p], 288, 288}}, B, 4 * zh, 4 * zw, 1, outs[p], MLAT, PC_EPI_NONE, nullptr, 0, nullptr, 0, false, &g));
+        }
+        return PC_OK;
+    }
     if (quality != 0 && c->topo.single_hyperprior) {   // one 640-output pair: the enhancement chain reads its channels [320:]
         PCCHK(hs(c, st, c->hss[1], z_hat, B, zh, zw, ls, MLAT));
         PCCHK(hs(c, st, c->hms[1], z_hat, B, zh, zw, lm, MLAT));
@@ -943,9 +1031,13 @@ extern "C" int pc_conv2d_nhwc(const float* x, int B, int H, int W, int Cin, cons
 }
 
 // Test aid (include/pcodec.h): the descriptor -> pc_conv_params with the codec's own tap tables, then the launcher
-extern "C" int pc_test_conv(const pc_test_conv_desc* d, int* plan, void* stream)
+extern "C" int pc_test_conv(const pc_test_conv_desc* d, int* plan, void* stream) { return pc_test_conv_g1aux(d, nullptr, plan, stream); }
+
+// pc_test_conv with group 1's own aux0 tensor (pc_conv_params::g1_aux0; the descriptor's layout is mirrored by tests and stays as it is)
+extern "C" int pc_test_conv_g1aux(const pc_test_conv_desc* d, const float* g1_aux0, int* plan, void* stream)
 {
     if (plan) plan[0] = plan[1] = 0;
+    if (g1_aux0 && (!d || d->ngroup != 2)) return PC_ERR_ARG;
     if (!d || !d->out || !d->w || d->nseg < 1 || d->nseg > PC_MAX_SEG || d->B <= 0 || d->H <= 0 || d->W <= 0) return PC_ERR_ARG;
     pc_conv_params q;
     std::memset(&q, 0, sizeof(q));
@@ -964,7 +1056,7 @@ extern "C" int pc_test_conv(const pc_test_conv_desc* d, int* plan, void* stream)
     else q.wlayout = d->kind == 1 ? pc_conv_weight_layout(1, d->Cin, d->Cout, 5) : 1;
     q.out = d->out; q.out_sb = d->out_sb; q.out_sy = d->out_sy; q.out_sx = d->out_sx; q.out_sc = d->out_sc;
     q.out_relu = d->out_relu;
-    if (d->ngroup == 2) { q.ngroup = 2; q.g1_seg0 = d->g1_seg0; q.g1_w = d->g1_w; q.g1_bias = d->g1_bias; q.g1_out = d->g1_out; }
+    if (d->ngroup == 2) { q.ngroup = 2; q.g1_seg0 = d->g1_seg0; q.g1_w = d->g1_w; q.g1_bias = d->g1_bias; q.g1_out = d->g1_out; q.g1_aux0 = g1_aux0; }
     return pc_conv_launch(q, (hipStream_t)stream, plan);
 }
 
@@ -1178,6 +1270,7 @@ extern "C" int pc_codec_set_option(pc_codec* c, const char* name, int value)
     else if (n == "lanes_dec") { if (value > 8) return PC_ERR_ARG; c->opt_lanes_dec = value; }
     else if (n == "host_threads") c->n_threads = value;
     else if (n == "profile_in_schedule") c->profile_in_schedule = value != 0;
+    else if (n == "group_siblings") { if (value > 1) return PC_ERR_ARG; c->opt_group_siblings = value; }
     else return PC_ERR_ARG;
     return PC_OK;
 }
@@ -1262,11 +1355,14 @@ int load_channel(pc_codec* c)
             h[0] = h[1];
             PCCHK(load_conv(c, p + ".8lo", 288, D0, 3, 0, &h[0].c8));
         }
+        PCCHK(load_hs_cat(c, {"h_scale_s", "h_mean_s"}, &c->hs_c0_cat2));
     } else {
         for (int k = 0; k < 2; ++k) {
             PCCHK(load_hs(c, "h_mean_s." + std::to_string(k), &c->hms[k]));
             PCCHK(load_hs(c, "h_scale_s." + std::to_string(k), &c->hss[k]));
         }
+        PCCHK(load_hs_cat(c, {"h_scale_s.0", "h_mean_s.0"}, &c->hs_c0_cat2));
+        PCCHK(load_hs_cat(c, {"h_scale_s.0", "h_mean_s.0", "h_scale_s.1", "h_mean_s.1"}, &c->hs_c0_cat4));
     }
     const int S = 5 - c->topo.support_deficit;                          // support_progressive_slices (CHProg_cnn.py:235-274)
     PCCHK(load_base_stacks(c));
@@ -1295,6 +1391,7 @@ int load_wacnn(pc_codec* c)
     PCCHK(load_ha(c, D0));
     PCCHK(load_hs(c, "h_mean_s", &c->hms[0]));
     PCCHK(load_hs(c, "h_scale_s", &c->hss[0]));
+    PCCHK(load_hs_cat(c, {"h_scale_s", "h_mean_s"}, &c->hs_c0_cat2));
     return load_base_stacks(c);
 }
 

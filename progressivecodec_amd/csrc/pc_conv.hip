@@ -1110,7 +1110,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TM * TN == 
     const bool fast = TM * TN == 1 && p.out_sc == 1 && (p.dense_out || !u0) && p.epi != PC_EPI_SE_ADD;
     // (dynamic indexing of the kernel-argument struct from inside a lambda makes hipcc copy the whole struct to scratch: hoisted)
     const int ooy_ph = p.ooy[phase], oox_ph = p.oox[phase];
-    const float* const aux0_p = p.aux0; const float* const aux1_p = p.aux1;
+    const float* const aux0_p = (p.ngroup == 2 && zsel == 1 && p.g1_aux0) ? p.g1_aux0 : p.aux0;   // (wave-uniform, as outp above)
+    const float* const aux1_p = p.aux1;
     const int ld0_v = p.ld0, ld1_v = p.ld1, epi_v = p.epi;
     // every kernel argument the tile code below needs, as plain locals: the lambdas must not touch `p` (with the 24 inlined epilogue bodies
     // referring to it hipcc gave up promoting the argument struct and copied all 1.6 KB of it to scratch at kernel entry)

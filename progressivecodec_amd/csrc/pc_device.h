@@ -7,7 +7,8 @@
 
 #include "../../include/pcodec.h"
 
-// Tuning scaffolding of the conv kernel (pc_conv.hip: PC_CONV_* tiles, policy, debug bits).  The tuning build (`make tuning` ->
+// Tuning scaffolding of the conv kernel (pc_conv.hip: PC_CONV_* tiles, policy, debug bits) and of the driver (pc_codec.hip:
+// PC_GROUP_SIBLINGS, the default of the option "group_siblings").  The tuning build (`make tuning` ->
 // libpcodec_tuning.so, -DPC_TUNING; tools/env_matrix.sh, tools/gpu_ab.sh, tools/conv_tune.py select it with PC_LIB) reads them from the
 // environment; the PRODUCT library reads none of them -- pc_tune() is the compiled-in default there.  What the product does read: PC_HOST_THREADS / PC_HOST_NO_PIN (host entropy-coding pool),
 // LOCAL_RANK / LOCAL_WORLD_SIZE (the launcher's), PC_TIMING, PC_PROFILE_CSV (diagnostics); the schedule is set per object with
@@ -85,9 +86,11 @@ struct pc_conv_params {
     // out = x * rsqrt(beta + gamma . x^2) with x = this layer's conv + bias.  Null: plain layer.
     const float* fg_gamma; const float* fg_beta;
     // grouped launch: a second GEMM of identical shape (cc_mean || cc_scale of one chain step) rides on blockIdx.z == 1;
-    // it differs only in its first input segment, weights, bias and output
+    // it differs only in its first input segment, weights, bias and output -- and, where the epilogue reads aux0 and g1_aux0 is set (the
+    // two branches' ResidualUnit tails of a window-attention module), in that tensor (same pixel stride ld0); null: both groups read aux0
     int ngroup;
     const float* g1_seg0; const float* g1_w; const float* g1_bias; float* g1_out;
+    const float* g1_aux0;
     const int* rowtab;                       // set by pc_conv_launch (layers with more than one tap): cached per layer geometry,
                                              // [M] input-pixel index of each GEMM row, then [nphase][M] tap-validity masks
     void* rowtab_cache;                      // pc_rowtab_cache* of the calling codec (null: the process-wide cache of the stand-alone entry points)

@@ -204,7 +204,7 @@ class _NativeCodecModule(_module_base()):
         return updated
 
     def set_option(self, name, value):
-        """pc_codec_set_option: schedule options of this object ("serial_schedule", "lanes_enc", "lanes_dec", "host_threads") -- results never
+        """pc_codec_set_option: schedule options of this object ("serial_schedule", "lanes_enc", "lanes_dec", "host_threads", "group_siblings") -- results never
         depend on them.  Options belong to the native handle: a reload of a finalised codec (load_state_dict) starts from the defaults."""
         check(lib().pc_codec_set_option(self._h, name.encode(), int(value)), f"pc_codec_set_option({name})")
         return self

@@ -29,6 +29,7 @@ run PC_CONV_TM=2 PC_CONV_TN=2
 run PC_CONV_ROWPERM=0
 run PC_CONV_ROWPERM_MIN=0
 run PC_CONV_GROUP_XCD=0
+run PC_GROUP_SIBLINGS=0
 run PC_HOST_THREADS=1
 echo "matrix failures: $fail"
 exit $fail
