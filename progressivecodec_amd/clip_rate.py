@@ -30,19 +30,17 @@ prediction, batching the decode across frames.
 """
 import collections
 import ctypes as C
-import struct
 from fractions import Fraction
 
 from . import clips
-from . import _imagelib
+from . import _imagelib, _tilecodec
 from ._lib import PC_OK
-from .clips import ENTRY_BYTES, HEADER_BYTES, _HEAD, _clip_changes, _clip_frames, _cut_into, _frame_index, clip_tile_bytes, source_table
-from .container import ContainerError
-from .frame_rate import max_tile
-from .frame_tiles import _admissible_window, pack_frame_tiled, stitch_frame
-from .frames import FORMATS, RANGES, UPSAMPLES, _MATRIX_ID, Frame, _check_enums, _frame_struct, _inv, bits_of, coefficients
+from ._tilecodec import max_tile  # noqa: F401
+from .clips import ENTRY_BYTES, HEADER_BYTES, _clip_frames, _cut_of, _frame_index, _frame_table, _source, clip_tile_bytes, source_table  # noqa: F401
+from .frame_tiles import pack_frame_tiled, stitch_frame
+from .frames import FORMATS, RANGES, UPSAMPLES, Frame, _check_enums, _frame_struct, bits_of, coefficients  # noqa: F401
 from .rate import allocate
-from .tiles import TileGrid, _check_tiles, grid_of, pack_tiled
+from .tiles import TileGrid, _check_tiles, _fit_tiles, grid_of, pack_tiled
 
 LIB_PATH = _imagelib.lib_path("clip_rate")
 
@@ -87,24 +85,12 @@ ClipRatePlan = collections.namedtuple("ClipRatePlan", "source items weights leve
 
 # -- the kernel ----------------------------------------------------------------------------------------------------------------------
 
-def _frame_table(fs, dev):
-    """the planes of every frame as batched views -> (the pc_cr_frame records in host memory, the same bytes on the device)"""
-    import torch
-    host = (Frame * len(fs))(*[_frame_struct(ts) for ts in fs])
-    return host, torch.frombuffer(bytearray(bytes(host)), dtype=torch.uint8).to(dev)
-
-
 def _sse_jobs_into(L, x, g, fmt, range, k, host, table, F, jobs_ptr, n, ws, nbytes, out, stream):
     rc = L.pc_clip_rate_sse_jobs(x.data_ptr(), x.stride(0), x.stride(1), x.stride(2), g.H, g.W, g.T, g.O, FORMATS[fmt], RANGES[range],
                                  k.kr, k.kg, k.kb, k.ib, k.ir, host, table.data_ptr(), F, jobs_ptr, n, ws.data_ptr(), nbytes, out.data_ptr(),
                                  stream)
     if rc != PC_OK:
         raise ClipRateError(rc, "pc_clip_rate_sse_jobs")
-
-
-def _fit_tiles(x, T):
-    """a tile tensor the kernel can take as it is, or its contiguous copy"""
-    return x if x.stride(3) == 1 and x.stride(2) >= T and min(x.stride()[:2]) >= 1 else x.contiguous()
 
 
 def _jobs(jobs, F, g):
@@ -132,8 +118,7 @@ def tile_distortion_jobs(x_hat_tiles, grid, frames, jobs, fmt, matrix="bt709", r
     full = grid_of(g.H, g.W, g.T, g.O)
     if (full.ny, full.nx) != (g.ny, g.nx):
         raise ValueError(f"{g}: the grid of a {g.H}x{g.W} frame is {full.ny}x{full.nx}")
-    if g.T > max_tile(fmt):
-        raise ValueError(f"tile must be at most {max_tile(fmt)} for the distortion sums of {fmt!r} to fit 63 bits, got {g.T}")
+    _tilecodec.tile_limit(g.T, fmt)
     fs, H, W = _clip_frames(frames, fmt)
     rows = _jobs(jobs, len(fs), full)
     x = x_hat_tiles
@@ -186,51 +171,13 @@ def parse_clip(buf):
     grid), F, table [F][ny*nx] of (offset, length), payload_start).  The same checks: the header, the geometry against pc_tiles_grid,
     that the whole table is there and that two entries are either equal or disjoint; an entry is checked against the buffer when
     its tile is asked for (tile_blob), so that a clip cut off inside its payload still gives the frames it holds completely."""
-    from . import tiles
-    if len(buf) < 4 or bytes(buf[:4]) != MAGIC:
-        raise ContainerError("not a PCS2 container")
-    if len(buf) < HEADER_BYTES:
-        raise ContainerError("truncated PCS2 header")
-    ver, f, m, r, u, bits, contract, H, W, T, O, ny, nx, F = struct.unpack_from(_HEAD, buf, 4)
-    if ver != VERSION:
-        raise ContainerError(f"unsupported PCS2 version {ver}")
-    fi, mi, ri, ui = _inv(FORMATS), _inv(_MATRIX_ID), _inv(RANGES), _inv(UPSAMPLES)
-    if f not in fi or m not in mi or r not in ri or u not in ui:
-        raise ContainerError(f"corrupt PCS2 header: fmt {f}, matrix {m}, range {r}, upsample {u}")
-    if bits != bits_of(fi[f]):
-        raise ContainerError(f"corrupt PCS2 header: {bits} bits for {fi[f]!r}")
-    cy, cx = C.c_int(0), C.c_int(0)
-    if max(H, W, T, O) >= 1 << 31 or tiles.lib().pc_tiles_grid(H, W, T, O, C.byref(cy), C.byref(cx)) != PC_OK:
-        raise ContainerError(f"corrupt PCS2 header: frame {H}x{W}, tile {T}, overlap {O}")
-    if (cy.value, cx.value) != (ny, nx):
-        raise ContainerError(f"corrupt PCS2 header: grid {ny}x{nx}, but a {H}x{W} frame in tiles of {T} with overlap {O} has {cy.value}x{cx.value}")
-    g = grid_of(H, W, T, O)
-    if (g.ny, g.nx) != (ny, nx):
-        raise ContainerError("corrupt PCS2 header: grid")
-    if F < 1:
-        raise ContainerError("corrupt PCS2 header: no frames")
-    n = ny * nx
-    start = HEADER_BYTES + ENTRY_BYTES * F * n
-    if len(buf) < start:
-        raise ContainerError("truncated PCS2 table")
-    flat = struct.unpack_from(f"<{2 * F * n}Q", buf, HEADER_BYTES)
-    pairs = list(zip(flat[0::2], flat[1::2]))
-    end = 0
-    for off, ln in sorted(set(pairs)):
-        if off < end:
-            raise ContainerError(f"corrupt PCS2 table: the entry ({off}, {ln}) overlaps another without being equal to it")
-        end = max(end, off + ln)
-    return {"fmt": fi[f], "matrix": mi[m], "range": ri[r], "upsample": ui[u], "bits": bits, "contract": contract, "grid": g, "F": F,
-            "table": [pairs[k * n:(k + 1) * n] for k in _range(F)], "payload_start": start}
+    return clips._parse(buf, MAGIC)
 
 
 def tile_blob(buf, hd, k, t):
     """clips.clip_tile_bytes for PCS2: the PCB1 container of tile t of frame k and its parsed header, after checking its table entry
     against the buffer, its header against the grid and the clip's contract, and that it holds exactly one level."""
-    tb, th = clip_tile_bytes(buf, hd, k, t)
-    if len(th["qualities"]) != 1:
-        raise ContainerError(f"frame {k}, tile {t} holds {len(th['qualities'])} levels, a PCS2 tile holds exactly one")
-    return tb, th
+    return clip_tile_bytes(buf, hd, k, t, one_level=True)
 
 
 def frame_container(buf, k):
@@ -278,73 +225,33 @@ def _to_size_arguments(frames, qualities, target_bytes, fmt, matrix, range, upsa
     """the argument checks of encode_clip_to_size (clip_tol_rate.encode_clip_to_size comes here, too), in its order and with its
     messages -> (qualities, step, plane weights, target_bytes, fs (the planes of frame k as batched views), the grid, importance
     flat or None, frame_weights as a list or None)"""
-    qualities = [float(q) for q in qualities]
-    if not qualities:
-        raise ValueError("at least one level")
+    qualities = _tilecodec.levels_of(qualities)
     _check_enums(fmt, matrix, range, upsample)
-    step = int(max_tiles_per_call)
-    if step < 1:
-        raise ValueError(f"max_tiles_per_call must be at least 1, got {max_tiles_per_call}")
-    pw = list(plane_weights)
-    if len(pw) != 3 or any(isinstance(v, bool) or not isinstance(v, int) or v < 0 for v in pw) or not any(pw):
-        raise ValueError(f"plane_weights must be three non-negative ints, not all zero, got {plane_weights!r}")
+    step = _tilecodec.tiles_per_call(max_tiles_per_call)
+    pw = _tilecodec.plane_weights_of(plane_weights)
     target_bytes = int(target_bytes)
     fs, H, W = _clip_frames(frames, fmt)
     g = clips._grid(H, W, tile, overlap)
-    if g.T > max_tile(fmt):
-        raise ValueError(f"tile must be at most {max_tile(fmt)} for the distortion sums of {fmt!r} to fit 63 bits, got {g.T}")
-    n, F = g.ny * g.nx, len(fs)
-    if importance is not None:
-        importance = list(importance)
-        if importance and isinstance(importance[0], (list, tuple)):
-            importance = [v for row in importance for v in row]
-        if len(importance) != n:
-            raise ValueError(f"importance needs one number per tile of the {g.ny}x{g.nx} grid, got {len(importance)}")
-    if frame_weights is not None:
-        frame_weights = list(frame_weights)
-        if len(frame_weights) != F:
-            raise ValueError(f"frame_weights needs one number per frame of the clip, {F} in all, got {len(frame_weights)}")
-    return qualities, step, pw, target_bytes, fs, g, importance, frame_weights
+    _tilecodec.tile_limit(g.T, fmt)
+    return qualities, step, pw, target_bytes, fs, g, _tilecodec.importance_of(importance, g), _tilecodec.frame_weights_of(frame_weights, len(fs))
 
 
-def _code_items(model, fs, g, items, qualities, fmt, range, upsample, mask_pol, k, step, measure):
-    """The work loop of encode_clip_to_size once the items are known (clip_tol_rate.encode_clip_to_size comes here with its own
-    measure): the items chunked by `step` ACROSS frames; per chunk one cut launch per frame present in it into one batch buffer,
-    model.compress_levels, model.decompress_levels, measure(a, b, decoded) -- the chunk is items[a:a + b], decoded[l]["x_hat"] its
-    tiles at level l; it returns one entry per item of the chunk and is done with the tiles when it returns -- and container.pack
-    of a single level per item and level -> (bufs[i][l], what measure returned, item by item)."""
-    import torch
-    from . import container
-    dev = fs[0][0].device
-    CL = clips.lib()
-    bufs, measured = [], []
-    with torch.cuda.device(dev):
-        didx = torch.tensor([t for _, t in items], dtype=torch.int32).to(dev)  # the cut takes the tiles
-    for a in _range(0, len(items), step):
-        chunk = items[a:a + step]
-        b = len(chunk)
-        with torch.cuda.device(dev):
-            x = torch.empty((b, 3, g.T, g.T), dtype=torch.float32, device=dev)
-            st = torch.cuda.current_stream(dev).cuda_stream
-            m0 = 0
-            while m0 < b:                                                      # one launch per frame present in the chunk
-                m1 = m0
-                while m1 < b and chunk[m1][0] == chunk[m0][0]:
-                    m1 += 1
-                _cut_into(CL, fs[chunk[m0][0]], fmt, range, upsample, k, g, didx[a + m0:].data_ptr(), m1 - m0, x[m0:m1], st)
-                m0 = m1
-        datas = model.compress_levels(x, qualities, mask_pol=mask_pol)
-        del x
-        strings = [d["strings"] for d in datas]
-        shape = datas[0]["shape"]
-        decoded = model.decompress_levels(strings, shape, qualities, mask_pol)
-        with torch.cuda.device(dev):
-            measured += measure(a, b, decoded)
-        del decoded
-        for m in _range(b):
-            bufs.append([container.pack([strings[l]], shape, [q], image_size=(g.T, g.T), mask_pol=mask_pol, image_index=m)
-                         for l, q in enumerate(qualities)])
-    return bufs, measured
+def _allocate_and_pack(bufs, dists, weights, items, source, target_bytes, g, fmt, matrix, range, upsample):
+    """What follows the work loop of encode_clip_to_size (and of clip_tol_rate's): bufs[i][l] the single-level containers of item
+    i, dists[i][l] what each level leaves -> (the PCS2 container of at most target_bytes bytes, levels[i], rates[i][l]).
+    ValueError, its message holding the minimum, if the cheapest level of every item does not fit."""
+    n, F = g.ny * g.nx, len(source)
+    rates = [[len(p) for p in row] for row in bufs]
+    fixed = HEADER_BYTES + ENTRY_BYTES * F * n
+    minimum = sum(min(r) for r in rates)
+    if fixed + minimum > target_bytes:
+        raise ValueError(f"target_bytes = {target_bytes} is below the minimum of {fixed + minimum} bytes: {fixed} bytes of header and table "
+                         f"and {minimum} bytes for every coded tile at its cheapest level")
+    levels = allocate(rates, dists, target_bytes - fixed, weights)
+    blobs = [[None] * n for _ in _range(F)]
+    for (f, t), row, l in zip(items, bufs, levels):
+        blobs[f][t] = row[l]
+    return pack_clip(blobs, source, g.H, g.W, g.T, g.O, fmt, matrix, range, upsample), levels, rates
 
 
 def encode_clip_to_size(model, frames, qualities, target_bytes, fmt, matrix="bt709", range="limited", upsample="linear", tile=512,
@@ -365,11 +272,7 @@ def encode_clip_to_size(model, frames, qualities, target_bytes, fmt, matrix="bt7
     qualities, step, pw, target_bytes, fs, g, importance, frame_weights = _to_size_arguments(
         frames, qualities, target_bytes, fmt, matrix, range, upsample, tile, overlap, plane_weights, importance, frame_weights, max_tiles_per_call)
     n, F, nl = g.ny * g.nx, len(fs), len(qualities)
-    if reuse and F > 1:
-        counts = _clip_changes(fs, fmt, g, upsample, 0, n).cpu()
-        source = source_table((counts != 0).any(dim=2).tolist())
-    else:
-        source = [[f] * n for f in _range(F)]
+    source = _source(fs, fmt, g, upsample, reuse)
     items, runs = items_of(source)
     weights = item_weights(items, runs, n, F, importance, frame_weights)
     k = coefficients(matrix)
@@ -382,26 +285,20 @@ def encode_clip_to_size(model, frames, qualities, target_bytes, fmt, matrix="bt7
         ws = torch.empty(nbytes // 8, dtype=torch.int64, device=dev)
 
     def measure(a, b, decoded):
-        d = torch.empty((nl, b, 3), dtype=torch.int64, device=dev)
-        st = torch.cuda.current_stream(dev).cuda_stream
-        for l, o in enumerate(decoded):                                        # one call per level, ordered on the stream: one workspace
-            xh = _fit_tiles(o["x_hat"], g.T)
-            _sse_jobs_into(L, xh, g, fmt, range, k, host, table, F, djobs[a:].data_ptr(), b, ws, nbytes, d[l], st)
-        d = d.tolist()                                                         # [levels][b][3]; synchronises: xh may go
+        with torch.cuda.device(dev):
+            d = torch.empty((nl, b, 3), dtype=torch.int64, device=dev)
+            st = torch.cuda.current_stream(dev).cuda_stream
+            for l, o in enumerate(decoded):                                    # one call per level, ordered on the stream: one workspace
+                xh = _fit_tiles(o["x_hat"], g.T)
+                _sse_jobs_into(L, xh, g, fmt, range, k, host, table, F, djobs[a:].data_ptr(), b, ws, nbytes, d[l], st)
+            d = d.tolist()                                                     # [levels][b][3]; synchronises: xh may go
         return [[[int(v) for v in d[l][m]] for l in _range(nl)] for m in _range(b)]
-    bufs, plane_dists = _code_items(model, fs, g, items, qualities, fmt, range, upsample, mask_pol, k, step, measure)
+    bufs, plane_dists = _tilecodec.encode_items(model, len(items), step, qualities, mask_pol, g.T,
+                                                _cut_of(fs, g, items, fmt, matrix, range, upsample), measure)
     del fs
-    rates = [[len(p) for p in row] for row in bufs]
     dists = [[pw[0] * v[0] + pw[1] * v[1] + pw[2] * v[2] for v in row] for row in plane_dists]
-    fixed = HEADER_BYTES + ENTRY_BYTES * F * n
-    minimum = sum(min(r) for r in rates)
-    if fixed + minimum > target_bytes:
-        raise ValueError(f"target_bytes = {target_bytes} is below the minimum of {fixed + minimum} bytes: {fixed} bytes of header and table "
-                         f"and {minimum} bytes for every coded tile at its cheapest level")
-    levels = allocate(rates, dists, target_bytes - fixed, weights)
+    buf, levels, rates = _allocate_and_pack(bufs, dists, weights, items, source, target_bytes, g, fmt, matrix, range, upsample)
     index = {it: i for i, it in enumerate(items)}
-    blobs = [[bufs[index[(f, t)]][levels[index[(f, t)]]] if source[f][t] == f else None for t in _range(n)] for f in _range(F)]
-    buf = pack_clip(blobs, source, g.H, g.W, g.T, g.O, fmt, matrix, range, upsample)
     chosen = [plane_dists[i][levels[i]] for i in _range(len(items))]
     sse = [[sum(chosen[index[(source[f][t], t)]][p] for t in _range(n)) for p in _range(3)] for f in _range(F)]
     predicted = sum(len(runs[i]) * dists[i][levels[i]] for i in _range(len(items)))
@@ -415,75 +312,12 @@ def decode_clip(model, buf, frames=None, level=-1, region=None, fmt=None, max_ti
     format or in `fmt` (as frame_tiles.decode_frame_tiled).  A PCS2 tile holds one level: level must be -1 or 0.  All byte work comes
     first, and every refusal is a ContainerError raised before the model is touched.  Among consecutive requested frames a byte range
     is decoded once: a tile whose table entry equals that of the frame handled just before reuses that frame's decoded float tile;
-    the rest are grouped by quality (ascending, tile order within a group: tiles._decode_per_tile_levels' rule) and decoded
+    the rest are grouped by quality (ascending, tile order within a group: the rule of a PCT2 container's tiles) and decoded
     max_tiles_per_call at a time.  Frame k is bit for bit frame_tiles.decode_frame_tiled(model, frame_container(buf, k), ...).  A PCS1
     container is passed to clips.decode_clip unchanged."""
-    import torch
-    from . import container
     if len(buf) >= 4 and bytes(buf[:4]) == clips.MAGIC:
         return clips.decode_clip(model, buf, frames=frames, level=level, region=region, fmt=fmt, max_tiles_per_call=max_tiles_per_call)
-    step = int(max_tiles_per_call)
-    if step < 1:
-        raise ValueError(f"max_tiles_per_call must be at least 1, got {max_tiles_per_call}")
+    step = _tilecodec.tiles_per_call(max_tiles_per_call)
     hd = parse_clip(buf)
-    try:
-        lv = int(level)
-    except (TypeError, ValueError):
-        lv = None
-    if lv not in (-1, 0):
-        raise ContainerError(f"a PCS2 container holds one level per tile: level must be -1 or 0, got {level!r}")
-    out_fmt = hd["fmt"] if fmt is None else fmt
-    _check_enums(out_fmt)
-    g = hd["grid"]
-    try:
-        window = _admissible_window(region, g.H, g.W)
-    except ValueError as e:
-        raise ContainerError(str(e)) from None
-    try:
-        wanted = list(_range(hd["F"])) if frames is None else [_frame_index(hd, k) for k in frames]
-    except TypeError:
-        raise ContainerError(f"frames must be an iterable of frame indices, got {frames!r}") from None
-    g = g.with_rect(g.covering(window))
-    need = [(g.ty0 + a) * g.nx + g.tx0 + b for a in _range(g.nty) for b in _range(g.ntx)]
-    # the byte work, all of it before the model is touched: per requested frame the tiles it takes from the frame handled just before
-    # it and, of the rest, the strings by quality; what a frame's tiles must share (latent shape, mask policy) is carried along
-    # with a reused tile, so that a frame is refused exactly where decode_frame_tiled of its own container is
-    todo, prev_entries, prev_keys = [], None, None
-    for k in wanted:
-        entries = [hd["table"][k][t] for t in need]
-        keys, groups, strings_of, first = [None] * len(need), {}, {}, None
-        for p, t in enumerate(need):
-            if prev_entries is not None and entries[p] == prev_entries[p]:
-                keys[p] = prev_keys[p]
-            else:
-                tb, _ = tile_blob(buf, hd, k, t)
-                strings, shape, qs, _, mask_pol = container.unpack(tb, levels=[0], expect_contract=False)      # checked below, once
-                keys[p] = (tuple(shape), mask_pol)
-                strings_of[p] = strings[0]
-                groups.setdefault(qs[0], []).append(p)
-            if first is None:
-                first = p
-            elif keys[p] != keys[first]:
-                raise ContainerError(f"frame {k}, tile {t} was coded as {keys[p]}, tile {need[first]} as {keys[first]}")
-        todo.append(([(q, groups[q]) for q in sorted(groups)], strings_of, keys[0]))
-        prev_entries, prev_keys = entries, keys
-    if todo and hd["contract"] != container.build_contract_id():
-        raise ContainerError(f"container was coded under numeric contract 0x{hd['contract']:08x}, this decoder implements "
-                             f"0x{container.build_contract_id():08x}: the streams are not interchangeable (DESIGN.md section 2)")
-    out, prev = [], None
-    for groups, strings_of, (shape, mask_pol) in todo:
-        x_hat = prev
-        if groups:
-            x_hat = None if len(strings_of) == len(need) else prev.clone()
-            for q, idx in groups:
-                for a in _range(0, len(idx), step):
-                    part = idx[a:a + step]
-                    ys = [[strings_of[p][0][i][0] for p in part] for i in _range(len(strings_of[part[0]][0]))]     # y_strings[slice][image]
-                    zs = [strings_of[p][1][0] for p in part]
-                    dec = model.decompress([ys, zs], shape, q, mask_pol)["x_hat"]
-                    if x_hat is None:
-                        x_hat = torch.empty((len(need),) + tuple(dec.shape[1:]), dtype=dec.dtype, device=dec.device)
-                    x_hat[torch.tensor(part, device=dec.device)] = dec
-        out.append(stitch_frame(x_hat, g, out_fmt, hd["matrix"], hd["range"], window=window))
-        prev = x_hat
-    return out
+    _tilecodec.one_level(level, "PCS2")
+    return clips._decode(model, buf, hd, True, frames, level, region, fmt, step, stitch_frame)

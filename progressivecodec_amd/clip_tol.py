@@ -34,9 +34,9 @@ import ctypes as C
 from fractions import Fraction
 
 from . import clips
-from . import _imagelib
+from . import _imagelib, _tilecodec
 from ._lib import PC_OK
-from .clips import _clip_frames, _encode_source
+from .clips import _clip_frames, _encode_source, _frame_table
 from .frames import FORMATS, UPSAMPLES, Frame, _check_enums, _frame_struct, bits_of
 
 LIB_PATH = _imagelib.lib_path("clip_tol")
@@ -129,13 +129,6 @@ def _tolerance(tolerance, fmt):
 ClipTolPlan = collections.namedtuple("ClipTolPlan", "source n_coded n_reused container_bytes stats worst")
 
 
-def _frame_table(fs, dev):
-    """the planes of every frame as batched views -> (the pc_ct_frame records in host memory, the same bytes on the device)"""
-    import torch
-    host = (Frame * len(fs))(*[_frame_struct(ts) for ts in fs])
-    return host, torch.frombuffer(bytearray(bytes(host)), dtype=torch.uint8).to(dev)
-
-
 def _scan(fs, fmt, g, upsample, tol):
     """scan_clip on checked arguments: fs[k] the planes of frame k as batched views"""
     import torch
@@ -194,9 +187,7 @@ def encode_clip(model, frames, qualities, fmt, matrix="bt709", range="limited", 
     qualities = [float(q) for q in qualities]
     _check_enums(fmt, matrix, range, upsample)
     tol = _tolerance(tolerance, fmt)
-    step = int(max_tiles_per_call)
-    if step < 1:
-        raise ValueError(f"max_tiles_per_call must be at least 1, got {max_tiles_per_call}")
+    step = _tilecodec.tiles_per_call(max_tiles_per_call)
     fs, H, W = _clip_frames(frames, fmt)
     g = clips._grid(H, W, tile, overlap)
     n, F = g.ny * g.nx, len(fs)

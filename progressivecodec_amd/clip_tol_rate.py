@@ -33,16 +33,15 @@ import ctypes as C
 from fractions import Fraction
 from math import gcd
 
-from . import _imagelib
+from . import _imagelib, _tilecodec
 from ._lib import PC_OK
-from .clip_rate import (_code_items, _fit_tiles, _frame_table, _to_size_arguments, decode_clip, frame_container, items_of, pack_clip,  # noqa: F401
-                        parse_clip)
+from .clip_rate import _allocate_and_pack, _to_size_arguments, decode_clip, frame_container, items_of, pack_clip, parse_clip  # noqa: F401
 from .clip_tol import Tolerance, _scan, _tolerance
-from .clips import ENTRY_BYTES, HEADER_BYTES, _clip_frames
-from .frame_rate import max_tile
+from .clips import ENTRY_BYTES, HEADER_BYTES, _clip_frames, _cut_of, _frame_table  # noqa: F401
+from .frame_rate import max_tile  # noqa: F401
 from .frames import FORMATS, RANGES, Frame, _check_enums, _frame_struct, coefficients
-from .rate import allocate
-from .tiles import TileGrid, _check_tiles, grid_of
+from .rate import allocate  # noqa: F401
+from .tiles import TileGrid, _check_tiles, _fit_tiles, grid_of
 
 LIB_PATH = _imagelib.lib_path("clip_tol_rate")
 
@@ -135,8 +134,7 @@ def tile_distortion_runs(x_hat_tiles, grid, frames, tiles, runs, fmt, matrix="bt
     full = grid_of(g.H, g.W, g.T, g.O)
     if (full.ny, full.nx) != (g.ny, g.nx):
         raise ValueError(f"{g}: the grid of a {g.H}x{g.W} frame is {full.ny}x{full.nx}")
-    if g.T > max_tile(fmt):
-        raise ValueError(f"tile must be at most {max_tile(fmt)} for the distortion sums of {fmt!r} to fit 63 bits, got {g.T}")
+    _tilecodec.tile_limit(g.T, fmt)
     fs, H, W = _clip_frames(frames, fmt)
     ts, rs = _runs(tiles, runs, len(fs), full)
     x = x_hat_tiles
@@ -253,30 +251,23 @@ def encode_clip_to_size(model, frames, qualities, target_bytes, fmt, matrix="bt7
     def measure(a, b, decoded):
         c = a // step
         ne = off[a + b] - off[a]
-        d = torch.empty((nl, ne, 3), dtype=torch.int64, device=dev)
-        stream = torch.cuda.current_stream(dev).cuda_stream
         host_off = (C.c_int32 * (b + 1))(*rebased[c])
-        for l, o in enumerate(decoded):                                        # one call per level, ordered on the stream: one workspace
-            xh = _fit_tiles(o["x_hat"], g.T)
-            _sse_runs_into(L, xh, g, fmt, range, k, host, table, F, words[a:].data_ptr(), host_off, words[at_offsets[c]:].data_ptr(),
-                           words[at_slots + off[a]:].data_ptr(), b, ne, ws, nbytes, d[l], stream)
-        d = d.tolist()                                                         # [levels][entries][3]; synchronises: xh may go
+        with torch.cuda.device(dev):
+            d = torch.empty((nl, ne, 3), dtype=torch.int64, device=dev)
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            for l, o in enumerate(decoded):                                    # one call per level, ordered on the stream: one workspace
+                xh = _fit_tiles(o["x_hat"], g.T)
+                _sse_runs_into(L, xh, g, fmt, range, k, host, table, F, words[a:].data_ptr(), host_off, words[at_offsets[c]:].data_ptr(),
+                               words[at_slots + off[a]:].data_ptr(), b, ne, ws, nbytes, d[l], stream)
+            d = d.tolist()                                                     # [levels][entries][3]; synchronises: xh may go
         return [[[[int(v) for v in d[l][e]] for e in _range(off[a + m] - off[a], off[a + m + 1] - off[a])] for l in _range(nl)]
                 for m in _range(b)]
-    bufs, plane_dists = _code_items(model, fs, g, items, qualities, fmt, range, upsample, mask_pol, k, step, measure)
+    bufs, plane_dists = _tilecodec.encode_items(model, len(items), step, qualities, mask_pol, g.T,
+                                                _cut_of(fs, g, items, fmt, matrix, range, upsample), measure)
     del fs
-    rates = [[len(p) for p in row] for row in bufs]
     dists = [[sum(fwi[f] * (pw[0] * v[0] + pw[1] * v[1] + pw[2] * v[2]) for f, v in zip(run, per_frame)) for per_frame in row]
              for run, row in zip(runs, plane_dists)]
-    fixed = HEADER_BYTES + ENTRY_BYTES * F * n
-    minimum = sum(min(r) for r in rates)
-    if fixed + minimum > target_bytes:
-        raise ValueError(f"target_bytes = {target_bytes} is below the minimum of {fixed + minimum} bytes: {fixed} bytes of header and table "
-                         f"and {minimum} bytes for every coded tile at its cheapest level")
-    levels = allocate(rates, dists, target_bytes - fixed, weights)
-    index = {it: i for i, it in enumerate(items)}
-    blobs = [[bufs[index[(f, t)]][levels[index[(f, t)]]] if source[f][t] == f else None for t in _range(n)] for f in _range(F)]
-    buf = pack_clip(blobs, source, g.H, g.W, g.T, g.O, fmt, matrix, range, upsample)
+    buf, levels, rates = _allocate_and_pack(bufs, dists, weights, items, source, target_bytes, g, fmt, matrix, range, upsample)
     chosen = [plane_dists[i][levels[i]] for i in _range(len(items))]                                   # [i][j][p]
     sse = [[0, 0, 0] for _ in _range(F)]
     predicted = 0

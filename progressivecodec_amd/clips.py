@@ -38,11 +38,11 @@ import ctypes as C
 import operator
 import struct
 
-from . import _imagelib
+from . import _imagelib, _tilecodec
 from ._lib import PC_OK
 from .container import ContainerError
 from .frame_tiles import _admissible_window, _one_frame, pack_frame_tiled, stitch_frame
-from .frames import FORMATS, RANGES, UPSAMPLES, _MATRIX_ID, Frame, _check_enums, _frame_struct, _frame_view, _inv, bits_of, coefficients
+from .frames import FORMATS, RANGES, UPSAMPLES, _MATRIX_ID, Frame, _check_enums, _frame_struct, _frame_view, bits_of, coefficients
 from .tiles import grid_of, pack_tiled
 
 LIB_PATH = _imagelib.lib_path("clips")
@@ -293,47 +293,33 @@ def pack_clip(blobs, source, H, W, tile, overlap, fmt, matrix, range, upsample, 
     return head + b"".join(table) + b"".join(payload)
 
 
+def _parse(buf, magic):
+    """parse_clip for the container whose magic this is: PCS1, or clip_rate's PCS2, which differs in nothing else"""
+    name = magic.decode()
+    if len(buf) < 4 or bytes(buf[:4]) != magic:
+        raise ContainerError(f"not a {name} container")
+    if len(buf) < HEADER_BYTES:
+        raise ContainerError(f"truncated {name} header")
+    ver, f, m, r, u, bits, contract, H, W, T, O, ny, nx, F = struct.unpack_from(_HEAD, buf, 4)
+    if ver != VERSION:
+        raise ContainerError(f"unsupported {name} version {ver}")
+    params = _tilecodec.frame_params(f, m, r, u, bits, name)
+    g, pairs, start = _tilecodec.tile_table(buf, HEADER_BYTES, H, W, T, O, ny, nx, F, f"{name} header", "frame", f"{name} table")
+    end = 0
+    for off, ln in sorted(set(pairs)):
+        if off < end:
+            raise ContainerError(f"corrupt {name} table: the entry ({off}, {ln}) overlaps another without being equal to it")
+        end = max(end, off + ln)
+    n = ny * nx
+    return dict(params, contract=contract, grid=g, F=F, table=[pairs[k * n:(k + 1) * n] for k in _range(F)], payload_start=start)
+
+
 def parse_clip(buf):
     """-> dict(fmt, matrix, range, upsample, bits, contract, grid (TileGrid, whole grid), F, table [F][ny*nx] of (offset, length),
     payload_start).  Checks the header, the geometry against pc_tiles_grid, that the whole table is there and that two entries are
     either equal or disjoint; an entry is checked against the buffer when its tile is asked for (clip_tile_bytes), so that a clip cut
     off inside its payload still gives the frames it holds completely.  ContainerError for everything else."""
-    from . import tiles
-    if len(buf) < 4 or bytes(buf[:4]) != MAGIC:
-        raise ContainerError("not a PCS1 container")
-    if len(buf) < HEADER_BYTES:
-        raise ContainerError("truncated PCS1 header")
-    ver, f, m, r, u, bits, contract, H, W, T, O, ny, nx, F = struct.unpack_from(_HEAD, buf, 4)
-    if ver != VERSION:
-        raise ContainerError(f"unsupported PCS1 version {ver}")
-    fi, mi, ri, ui = _inv(FORMATS), _inv(_MATRIX_ID), _inv(RANGES), _inv(UPSAMPLES)
-    if f not in fi or m not in mi or r not in ri or u not in ui:
-        raise ContainerError(f"corrupt PCS1 header: fmt {f}, matrix {m}, range {r}, upsample {u}")
-    if bits != bits_of(fi[f]):
-        raise ContainerError(f"corrupt PCS1 header: {bits} bits for {fi[f]!r}")
-    cy, cx = C.c_int(0), C.c_int(0)
-    if max(H, W, T, O) >= 1 << 31 or tiles.lib().pc_tiles_grid(H, W, T, O, C.byref(cy), C.byref(cx)) != PC_OK:
-        raise ContainerError(f"corrupt PCS1 header: frame {H}x{W}, tile {T}, overlap {O}")
-    if (cy.value, cx.value) != (ny, nx):
-        raise ContainerError(f"corrupt PCS1 header: grid {ny}x{nx}, but a {H}x{W} frame in tiles of {T} with overlap {O} has {cy.value}x{cx.value}")
-    g = grid_of(H, W, T, O)
-    if (g.ny, g.nx) != (ny, nx):
-        raise ContainerError("corrupt PCS1 header: grid")
-    if F < 1:
-        raise ContainerError("corrupt PCS1 header: no frames")
-    n = ny * nx
-    start = HEADER_BYTES + ENTRY_BYTES * F * n
-    if len(buf) < start:
-        raise ContainerError("truncated PCS1 table")
-    flat = struct.unpack_from(f"<{2 * F * n}Q", buf, HEADER_BYTES)
-    pairs = list(zip(flat[0::2], flat[1::2]))
-    end = 0
-    for off, ln in sorted(set(pairs)):
-        if off < end:
-            raise ContainerError(f"corrupt PCS1 table: the entry ({off}, {ln}) overlaps another without being equal to it")
-        end = max(end, off + ln)
-    return {"fmt": fi[f], "matrix": mi[m], "range": ri[r], "upsample": ui[u], "bits": bits, "contract": contract, "grid": g, "F": F,
-            "table": [pairs[k * n:(k + 1) * n] for k in _range(F)], "payload_start": start}
+    return _parse(buf, MAGIC)
 
 
 def _frame_index(hd, k):
@@ -346,20 +332,12 @@ def _frame_index(hd, k):
     return k
 
 
-def clip_tile_bytes(buf, hd, k, t):
+def clip_tile_bytes(buf, hd, k, t, one_level=False):
     """The PCB1 container of tile t of frame k and its parsed header, after checking its table entry against the buffer and its
-    header against the grid and the clip's contract."""
-    from . import container
-    off, n = hd["table"][k][t]
-    if off < hd["payload_start"] or off + n > len(buf):
-        raise ContainerError(f"frame {k}, tile {t}: table entry ({off}, {n}) points outside the {len(buf)} bytes at hand (truncated or corrupt)")
-    tb = bytes(buf[off:off + n])
-    th = container.parse_header(tb)
-    T = hd["grid"].T
-    if th["image_size"] != (T, T) or tuple(th["shape"]) != (T // 64, T // 64):
-        raise ContainerError(f"frame {k}, tile {t}: its container holds a {th['image_size'][0]}x{th['image_size'][1]} image, not a {T}x{T} tile")
-    if th["contract"] != hd["contract"]:
-        raise ContainerError(f"frame {k}, tile {t}: numeric contract 0x{th['contract']:08x}, the clip's is 0x{hd['contract']:08x}")
+    header against the grid and the clip's contract; with one_level (PCS2, clip_rate.py) also that it holds exactly one level."""
+    tb, th = _tilecodec.entry_bytes(buf, hd, hd["table"][k][t], f"frame {k}, tile {t}", "clip")
+    if one_level and len(th["qualities"]) != 1:
+        raise ContainerError(f"frame {k}, tile {t} holds {len(th['qualities'])} levels, a PCS2 tile holds exactly one")
     return tb, th
 
 
@@ -375,38 +353,52 @@ def frame_container(buf, k):
 
 # -- through the codec ---------------------------------------------------------------------------------------------------------------
 
-def _encode_source(model, fs, g, source, qualities, fmt, matrix, range, upsample, mask_pol, step):
-    """encode_clip once the source table is known (clip_tol.encode_clip comes here with its own): fs[k] the planes of frame k as
-    batched views, everything checked -> (the PCS1 container, the number of coded tiles).  The work list -- every (f, t) with
-    source[f][t] == f, in (f, t) order -- is chunked by `step` across frames: per chunk one cut launch per frame present in it into
-    one batch buffer, then model.compress_levels, then container.pack per tile."""
+def _frame_table(fs, dev):
+    """the planes of every frame as batched views -> (the frame records in host memory, the same bytes on the device)"""
     import torch
-    from . import container
-    n, F = g.ny * g.nx, len(fs)
-    work = [(f, t) for f in _range(F) for t in _range(n) if source[f][t] == f]
+    host = (Frame * len(fs))(*[_frame_struct(ts) for ts in fs])
+    return host, torch.frombuffer(bytearray(bytes(host)), dtype=torch.uint8).to(dev)
+
+
+def _cut_of(fs, g, work, fmt, matrix, range, upsample):
+    """-> cut(a, b) for _tilecodec.encode_items: the tiles work[a:a + b] -- (frame, tile) pairs in (frame, tile) order -- as one batch
+    buffer, one cut launch per frame present in the chunk.  The tile list of the whole clip is uploaded once, here."""
+    import torch
     k = coefficients(matrix)
     dev = fs[0][0].device
     L = lib()
-    blobs = [[None] * n for _ in _range(F)]
     with torch.cuda.device(dev):
         didx = torch.tensor([t for _, t in work], dtype=torch.int32).to(dev)
-    for a in _range(0, len(work), step):
-        chunk = work[a:a + step]
+
+    def cut(a, b):
         with torch.cuda.device(dev):
-            x = torch.empty((len(chunk), 3, g.T, g.T), dtype=torch.float32, device=dev)
+            x = torch.empty((b, 3, g.T, g.T), dtype=torch.float32, device=dev)
             st = torch.cuda.current_stream(dev).cuda_stream
-            m0 = 0
-            while m0 < len(chunk):                                           # one launch per frame present in the chunk
-                m1 = m0
-                while m1 < len(chunk) and chunk[m1][0] == chunk[m0][0]:
-                    m1 += 1
-                _cut_into(L, fs[chunk[m0][0]], fmt, range, upsample, k, g, didx[a + m0:].data_ptr(), m1 - m0, x[m0:m1], st)
-                m0 = m1
-        datas = model.compress_levels(x, qualities, mask_pol=mask_pol)
-        del x
-        strings = [d["strings"] for d in datas]
-        for b, (f, t) in enumerate(chunk):
-            blobs[f][t] = container.pack(strings, datas[0]["shape"], qualities, image_size=(g.T, g.T), mask_pol=mask_pol, image_index=b)
+            for f, m0, m1 in _tilecodec.frame_pieces(work[a:a + b]):
+                _cut_into(L, fs[f], fmt, range, upsample, k, g, didx[a + m0:].data_ptr(), m1 - m0, x[m0:m1], st)
+        return x
+    return cut
+
+
+def _source(fs, fmt, g, upsample, reuse):
+    """the source table of a clip: with reuse, from one clip_changes and one device-to-host copy of its result"""
+    n, F = g.ny * g.nx, len(fs)
+    if reuse and F > 1:
+        counts = _clip_changes(fs, fmt, g, upsample, 0, n).cpu()
+        return source_table((counts != 0).any(dim=2).tolist())
+    return [[f] * n for f in _range(F)]
+
+
+def _encode_source(model, fs, g, source, qualities, fmt, matrix, range, upsample, mask_pol, step):
+    """encode_clip once the source table is known (clip_tol.encode_clip comes here with its own): fs[k] the planes of frame k as
+    batched views, everything checked -> (the PCS1 container, the number of coded tiles).  The work list -- every (f, t) with
+    source[f][t] == f, in (f, t) order -- is chunked by `step` across frames (_tilecodec.encode_items over _cut_of's cut)."""
+    n, F = g.ny * g.nx, len(fs)
+    work = [(f, t) for f in _range(F) for t in _range(n) if source[f][t] == f]
+    bufs = _tilecodec.encode_items(model, len(work), step, qualities, mask_pol, g.T, _cut_of(fs, g, work, fmt, matrix, range, upsample))
+    blobs = [[None] * n for _ in _range(F)]
+    for (f, t), b in zip(work, bufs):
+        blobs[f][t] = b
     return pack_clip(blobs, source, g.H, g.W, g.T, g.O, fmt, matrix, range, upsample), len(work)
 
 
@@ -421,46 +413,19 @@ def encode_clip(model, frames, qualities, fmt, matrix="bt709", range="limited", 
     frames are laid out in memory; frame_container(buf, k) is frame_tiles.encode_frame_tiled of frame k."""
     qualities = [float(q) for q in qualities]
     _check_enums(fmt, matrix, range, upsample)
-    step = int(max_tiles_per_call)
-    if step < 1:
-        raise ValueError(f"max_tiles_per_call must be at least 1, got {max_tiles_per_call}")
+    step = _tilecodec.tiles_per_call(max_tiles_per_call)
     fs, H, W = _clip_frames(frames, fmt)
     g = _grid(H, W, tile, overlap)
     n, F = g.ny * g.nx, len(fs)
-    if reuse and F > 1:
-        counts = _clip_changes(fs, fmt, g, upsample, 0, n).cpu()
-        source = source_table((counts != 0).any(dim=2).tolist())
-    else:
-        source = [[f] * n for f in _range(F)]
+    source = _source(fs, fmt, g, upsample, reuse)
     buf, n_coded = _encode_source(model, fs, g, source, qualities, fmt, matrix, range, upsample, mask_pol, step)
     return buf, ClipPlan(source, n_coded, F * n - n_coded, len(buf))
 
 
-def _level_strings(tb, th, level, where):
-    """one level of one tile's PCB1 container -> (the key tiles of one codec call must share, its strings)"""
-    from . import container
-    nl = len(th["qualities"])
-    lv = int(level) + nl if int(level) < 0 else int(level)
-    if not 0 <= lv < nl:
-        raise ContainerError(f"{where}: no level {level} among {nl}")
-    strings, shape, qs, _, mask_pol = container.unpack(tb, levels=[lv], expect_contract=False)          # checked by decode_clip, once
-    return (tuple(shape), qs[0], mask_pol, len(strings[0][0])), strings[0]
-
-
-def decode_clip(model, buf, frames=None, level=-1, region=None, fmt=None, max_tiles_per_call=32):
-    """One level of the frames `frames` (an iterable of indices, default all of them, in the order given) of a PCS1 container -> a list
-    of frames (tuples of planes without a batch axis) on the model's device, or of their admissible region = (y0, x0, h, w), in the
-    stored format or in `fmt` (as frame_tiles.decode_frame_tiled).  Only the tiles that cover the region are read.  Among consecutive
-    requested frames a byte range is decoded once: a tile whose table entry equals that of the frame handled just before reuses that
-    frame's decoded float tile; the rest are decoded max_tiles_per_call at a time.  Device memory is bounded by two frames' tile sets
-    plus one call.  Every refusal is a ContainerError raised before the model is touched.  Frame k is bit for bit
-    frame_tiles.decode_frame_tiled(model, frame_container(buf, k), ...)."""
-    import torch
-    from . import container
-    step = int(max_tiles_per_call)
-    if step < 1:
-        raise ValueError(f"max_tiles_per_call must be at least 1, got {max_tiles_per_call}")
-    hd = parse_clip(buf)
+def _decode(model, buf, hd, one_level, frames, level, region, fmt, step, stitch):
+    """decode_clip on a parsed header: of a PCS1 container (one level of tiles that hold several), or with one_level of a PCS2
+    container (clip_rate.decode_clip: the one level every tile holds; tiles may differ in quality).  All byte work comes first, and
+    every refusal is a ContainerError raised before the model is touched.  stitch is the caller's stitch_frame."""
     out_fmt = hd["fmt"] if fmt is None else fmt
     _check_enums(out_fmt)
     g = hd["grid"]
@@ -474,44 +439,46 @@ def decode_clip(model, buf, frames=None, level=-1, region=None, fmt=None, max_ti
         raise ContainerError(f"frames must be an iterable of frame indices, got {frames!r}") from None
     g = g.with_rect(g.covering(window))
     need = [(g.ty0 + a) * g.nx + g.tx0 + b for a in _range(g.nty) for b in _range(g.ntx)]
-    # the byte work, all of it before the model is touched: per requested frame the tiles it takes from the frame handled just before
-    # it (`keep`: position -> position, the same here) and the strings of the rest, which must agree in what a codec call shares
-    jobs, prev_entries = [], None
+    # per requested frame the tiles it takes from the frame handled just before it and, of the rest, the strings by quality (one
+    # quality where the tiles hold several levels: it is part of what they must share).  Under one_level, what a frame's tiles
+    # must share is carried along with a reused tile, so that a frame is refused exactly where decode_frame_tiled of its own
+    # container is; otherwise the fresh tiles are held to each other only
+    todo, prev_entries, prev_keys = [], None, None
     for k in wanted:
         entries = [hd["table"][k][t] for t in need]
-        fresh, common = [], None
+        keys, groups, strings_of, first, shared = [None] * len(need), {}, {}, None, (None, None)
         for p, t in enumerate(need):
             if prev_entries is not None and entries[p] == prev_entries[p]:
-                continue
-            tb, th = clip_tile_bytes(buf, hd, k, t)
-            key, strings = _level_strings(tb, th, level, f"frame {k}, tile {t}")
-            if common is None:
-                common = key
-            elif key != common:
-                raise ContainerError(f"frame {k}, tile {t} was coded as {key}, tile {need[fresh[0][0]]} as {common}")
-            fresh.append((p, strings))
-        jobs.append((fresh, common))
-        prev_entries = entries
-    if jobs and hd["contract"] != container.build_contract_id():
-        raise ContainerError(f"container was coded under numeric contract 0x{hd['contract']:08x}, this decoder implements "
-                             f"0x{container.build_contract_id():08x}: the streams are not interchangeable (DESIGN.md section 2)")
+                if not one_level:
+                    continue
+                keys[p] = prev_keys[p]
+            else:
+                tb, th = clip_tile_bytes(buf, hd, k, t, one_level)
+                shape, q, mask_pol, strings = _tilecodec.level_strings(tb, th, 0 if one_level else level, f"frame {k}, tile {t}: ")
+                keys[p] = (shape, mask_pol) if one_level else (shape, q, mask_pol, len(strings[0]))
+                strings_of[p], shared = strings, (shape, mask_pol)
+                groups.setdefault(q, []).append(p)
+            if first is None:
+                first = p
+            _tilecodec.same_coding(keys[p], keys[first], f"frame {k}, tile {t}", f"tile {need[first]}")
+        todo.append((sorted(groups.items()), strings_of, shared))
+        prev_entries, prev_keys = entries, keys
+    if todo:
+        _tilecodec.check_contract(hd["contract"])
     out, prev = [], None
-    for fresh, common in jobs:
-        x_hat = prev
-        if fresh:
-            shape, q, mask_pol, ns = common
-            x_hat = None if len(fresh) == len(need) else prev.clone()
-            for a in _range(0, len(fresh), step):
-                part = fresh[a:a + step]
-                ys = [[s[0][i][0] for _, s in part] for i in _range(ns)]            # y_strings[slice][image]
-                zs = [s[1][0] for _, s in part]
-                dec = model.decompress([ys, zs], shape, q, mask_pol)["x_hat"]
-                if x_hat is None:
-                    if len(part) == len(need):
-                        x_hat = dec
-                        break
-                    x_hat = torch.empty((len(need),) + tuple(dec.shape[1:]), dtype=dec.dtype, device=dec.device)
-                x_hat[torch.tensor([p for p, _ in part], device=dec.device)] = dec
-        out.append(stitch_frame(x_hat, g, out_fmt, hd["matrix"], hd["range"], window=window))
-        prev = x_hat
+    for groups, strings_of, shared in todo:
+        prev = _tilecodec.decode_positions(model, strings_of, groups, *shared, step, len(need), prev)
+        out.append(stitch(prev, g, out_fmt, hd["matrix"], hd["range"], window=window))
     return out
+
+
+def decode_clip(model, buf, frames=None, level=-1, region=None, fmt=None, max_tiles_per_call=32):
+    """One level of the frames `frames` (an iterable of indices, default all of them, in the order given) of a PCS1 container -> a list
+    of frames (tuples of planes without a batch axis) on the model's device, or of their admissible region = (y0, x0, h, w), in the
+    stored format or in `fmt` (as frame_tiles.decode_frame_tiled).  Only the tiles that cover the region are read.  Among consecutive
+    requested frames a byte range is decoded once: a tile whose table entry equals that of the frame handled just before reuses that
+    frame's decoded float tile; the rest are decoded max_tiles_per_call at a time.  Device memory is bounded by two frames' tile sets
+    plus one call.  Every refusal is a ContainerError raised before the model is touched.  Frame k is bit for bit
+    frame_tiles.decode_frame_tiled(model, frame_container(buf, k), ...)."""
+    step = _tilecodec.tiles_per_call(max_tiles_per_call)
+    return _decode(model, buf, parse_clip(buf), False, frames, level, region, fmt, step, stitch_frame)

@@ -21,13 +21,14 @@ target PSNR (the dual problem), 4:2:2 / 4:4:4 and other chroma sitings, perceptu
 import collections
 import ctypes as C
 
-from . import _imagelib
+from . import _imagelib, _tilecodec
 from ._lib import PC_OK
+from ._tilecodec import max_tile  # noqa: F401
 from .frame_tiles import HEADER_BYTES as FRAME_HEADER_BYTES
 from .frame_tiles import FrameTilesError, _one_frame, pack_frame_tiled
 from .frames import FORMATS, RANGES, UPSAMPLES, Frame, _check_enums, _frame_struct, coefficients
 from .rate import TABLE_ENTRY_BYTES, allocate
-from .tiles import HEADER_BYTES, TileGrid, _check_tiles, grid_of, pack_tiled
+from .tiles import HEADER_BYTES, TileGrid, _check_tiles, _fit_tiles, grid_of, pack_tiled
 
 LIB_PATH = _imagelib.lib_path("frame_rate")
 
@@ -63,11 +64,6 @@ class FrameRateError(_imagelib.ImageLibError):
 FrameRatePlan = collections.namedtuple("FrameRatePlan", "levels rates dists plane_dists den container_bytes predicted sse")
 
 
-def max_tile(fmt):
-    """the largest tile whose distortion sums fit 63 bits: T^4 (2^n - 1)^2 < 2^60"""
-    return 1024 if fmt == "p010" else 2048
-
-
 def frame_tile_distortion(x_hat_tiles, grid, ref, fmt, matrix="bt709", range="limited", first_tile=0):
     """x_hat_tiles: float32 cuda [n,3,T,T], the decoded tiles first_tile .. first_tile + n - 1 of grid's row-major ny x nx grid (a
     linear range, not a rectangle; grid's own rectangle is ignored; any tile / channel / row strides, unit stride along a row), ref: the
@@ -80,8 +76,7 @@ def frame_tile_distortion(x_hat_tiles, grid, ref, fmt, matrix="bt709", range="li
     full = grid_of(g.H, g.W, g.T, g.O)
     if (full.ny, full.nx) != (g.ny, g.nx):
         raise ValueError(f"{g}: the grid of a {g.H}x{g.W} frame is {full.ny}x{full.nx}")
-    if g.T > max_tile(fmt):
-        raise ValueError(f"tile must be at most {max_tile(fmt)} for the distortion sums of {fmt!r} to fit 63 bits, got {g.T}")
+    _tilecodec.tile_limit(g.T, fmt)
     x = x_hat_tiles
     n = int(x.shape[0]) if torch.is_tensor(x) and x.dim() == 4 else 0
     first_tile = int(first_tile)
@@ -94,8 +89,7 @@ def frame_tile_distortion(x_hat_tiles, grid, ref, fmt, matrix="bt709", range="li
         raise ValueError(f"ref must be the {g.H}x{g.W} frame on {x.device}, got {rH}x{rW} on {rts[0].device}")
     if x.device.type != "cuda":
         raise ValueError(f"x_hat_tiles must be on a GPU (there is no CPU fallback), got {x.device}")
-    if x.stride(3) != 1 or x.stride(2) < g.T or min(x.stride()[:2]) < 1:
-        x = x.contiguous()
+    x = _fit_tiles(x, g.T)
     k = coefficients(matrix)
     L = lib()
     rst = _frame_struct(rts)
@@ -137,60 +131,40 @@ def encode_frame_tiled_to_size(model, planes, qualities, target_bytes, fmt, matr
     time, so a call holds at most max_tiles_per_call * (1 + len(qualities)) tile tensors on the device; neither the bytes nor the
     plan depend on it.  The container holds a PCT2 container (one level per tile); frame_tiles.decode_frame_tiled reads it."""
     import torch
-    from . import container, frame_tiles
-    qualities = [float(q) for q in qualities]
-    if not qualities:
-        raise ValueError("at least one level")
+    from . import frame_tiles
+    qualities = _tilecodec.levels_of(qualities)
     _check_enums(fmt, matrix, range, upsample)
-    step = int(max_tiles_per_call)
-    if step < 1:
-        raise ValueError(f"max_tiles_per_call must be at least 1, got {max_tiles_per_call}")
-    pw = list(plane_weights)
-    if len(pw) != 3 or any(isinstance(v, bool) or not isinstance(v, int) or v < 0 for v in pw) or not any(pw):
-        raise ValueError(f"plane_weights must be three non-negative ints, not all zero, got {plane_weights!r}")
+    step = _tilecodec.tiles_per_call(max_tiles_per_call)
+    pw = _tilecodec.plane_weights_of(plane_weights)
     target_bytes = int(target_bytes)
     ts, H, W = _one_frame(planes, fmt, "planes")
     g = grid_of(H, W, tile, overlap)
-    if g.T > max_tile(fmt):
-        raise ValueError(f"tile must be at most {max_tile(fmt)} for the distortion sums of {fmt!r} to fit 63 bits, got {g.T}")
+    _tilecodec.tile_limit(g.T, fmt)
     n = g.ny * g.nx
-    if importance is not None:
-        importance = list(importance)
-        if importance and isinstance(importance[0], (list, tuple)):
-            importance = [v for row in importance for v in row]
-        if len(importance) != n:
-            raise ValueError(f"importance needs one number per tile of the {g.ny}x{g.nx} grid, got {len(importance)}")
+    importance = _tilecodec.importance_of(importance, g)
     k = coefficients(matrix)
     dev = ts[0].device
     src = _frame_struct(ts)
     CL = frame_tiles.lib()
-    bufs, rates, plane_dists = [], [], []
-    for a in _range(0, n, step):
-        b = min(step, n - a)
+
+    def cut(a, b):
         with torch.cuda.device(dev):
             x = torch.empty((b, 3, g.T, g.T), dtype=torch.float32, device=dev)
             m0 = 0
-            while m0 < b:                                               # the linear range a .. a + b - 1, one piece per grid row
-                i, j = divmod(a + m0, g.nx)
-                m = min(b - m0, g.nx - j)
+            for i, j, m in _tilecodec.row_pieces(a, b, g.nx):
                 rc = CL.pc_frame_tiles_cut(C.byref(src), FORMATS[fmt], RANGES[range], UPSAMPLES[upsample], k.a, k.b, k.c, k.d, H, W, g.T,
                                            g.O, i, j, 1, m, x[m0:].data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
                 if rc != PC_OK:
                     raise FrameTilesError(rc, "pc_frame_tiles_cut")
                 m0 += m
-        datas = model.compress_levels(x, qualities, mask_pol=mask_pol)
-        del x
-        strings = [d["strings"] for d in datas]
-        shape = datas[0]["shape"]
-        decoded = model.decompress_levels(strings, shape, qualities, mask_pol)
+        return x
+
+    def measure(a, b, decoded):
         d = torch.stack([frame_tile_distortion(o["x_hat"], g, ts, fmt, matrix, range, a) for o in decoded], 1).tolist()     # [b][levels][3]
-        del decoded
-        for t in _range(b):
-            bufs.append([container.pack([strings[l]], shape, [q], image_size=(g.T, g.T), mask_pol=mask_pol, image_index=t)
-                         for l, q in enumerate(qualities)])
-            rates.append([TABLE_ENTRY_BYTES + len(p) for p in bufs[-1]])
-            plane_dists.append([[int(v) for v in row] for row in d[t]])
+        return [[[int(v) for v in row] for row in per_level] for per_level in d]
+    bufs, plane_dists = _tilecodec.encode_items(model, n, step, qualities, mask_pol, g.T, cut, measure)
     del ts
+    rates = [[TABLE_ENTRY_BYTES + len(p) for p in row] for row in bufs]
     dists = [[pw[0] * v[0] + pw[1] * v[1] + pw[2] * v[2] for v in row] for row in plane_dists]
     levels = allocate(rates, dists, target_bytes - FRAME_HEADER_BYTES - HEADER_BYTES, importance)
     inner = pack_tiled([bufs[t][levels[t]] for t in _range(n)], g.H, g.W, g.T, g.O, per_tile_levels=True)

@@ -28,11 +28,11 @@ compress_with_ac.
 import ctypes as C
 import struct
 
-from . import _imagelib
+from . import _imagelib, _tilecodec
 from ._lib import PC_OK
-from .frames import (FORMATS, RANGES, UPSAMPLES, _MATRIX_ID, Distortion, Frame, _check_enums, _frame_struct, _frame_view, _inv, bits_of,
-                     coefficients, empty_frame)
-from .tiles import TileGrid, _check_tiles, _window, grid_of
+from .frames import (FORMATS, RANGES, UPSAMPLES, _MATRIX_ID, Distortion, Frame, _check_enums, _frame_struct, _frame_view, bits_of, coefficients,
+                     empty_frame)
+from .tiles import TileGrid, _check_tiles, _fit_tiles, _window, grid_of
 
 LIB_PATH = _imagelib.lib_path("frame_tiles")
 
@@ -45,8 +45,6 @@ MAGIC = b"PCG1"
 VERSION = 1
 _HEAD = "<BBBBBB"                         # version, fmt, matrix, range, upsample, bits
 HEADER_BYTES = 4 + struct.calcsize(_HEAD)
-
-_range = range                            # the functions below take a parameter of that name
 
 
 def _prototypes():
@@ -158,8 +156,7 @@ def stitch_frame(x_hat_tiles, grid, fmt, matrix="bt709", range="limited", window
             raise ValueError(f"ref must be the {g.H}x{g.W} frame on {x.device}, got {rH}x{rW} on {rts[0].device}")
     if x.device.type != "cuda":
         raise ValueError(f"x_hat_tiles must be on a GPU (there is no CPU fallback), got {x.device}")
-    if x.stride(3) != 1 or x.stride(2) < g.T or min(x.stride()[:2]) < 1:
-        x = x.contiguous()
+    x = _fit_tiles(x, g.T)
     k = coefficients(matrix)
     L = lib()
     with torch.cuda.device(x.device):
@@ -227,18 +224,14 @@ def parse_frame_tiled(buf):
     ver, f, m, r, u, bits = struct.unpack_from(_HEAD, buf, 4)
     if ver != VERSION:
         raise container.ContainerError(f"unsupported PCG1 version {ver}")
-    fi, mi, ri, ui = _inv(FORMATS), _inv(_MATRIX_ID), _inv(RANGES), _inv(UPSAMPLES)
-    if f not in fi or m not in mi or r not in ri or u not in ui:
-        raise container.ContainerError(f"corrupt PCG1 header: fmt {f}, matrix {m}, range {r}, upsample {u}")
-    if bits != bits_of(fi[f]):
-        raise container.ContainerError(f"corrupt PCG1 header: {bits} bits for {fi[f]!r}")
+    params = _tilecodec.frame_params(f, m, r, u, bits, "PCG1")
     inner = bytes(buf[HEADER_BYTES:])
     try:
         hd = tiles.parse_tiled(inner)
     except container.ContainerError as e:
         raise container.ContainerError(f"PCG1: the inner container does not parse: {e}") from None
     g = hd["grid"]
-    return {"fmt": fi[f], "matrix": mi[m], "range": ri[r], "upsample": ui[u], "bits": bits, "H": g.H, "W": g.W, "inner": inner, "tiled": hd}
+    return dict(params, H=g.H, W=g.W, inner=inner, tiled=hd)
 
 
 def encode_frame_tiled(model, planes, qualities, fmt, matrix="bt709", range="limited", upsample="linear", tile=512, overlap=0,
@@ -246,18 +239,11 @@ def encode_frame_tiled(model, planes, qualities, fmt, matrix="bt709", range="lim
     """frame -> one PCG1 container (bytes) holding every level of `qualities` for every tile.  The tiles are coded max_tiles_per_call
     at a time as one batch each (model.compress_levels), which bounds the device memory a call needs whatever the frame's size; the
     bytes do not depend on it.  The PCT1 container inside is what tiles.pack_tiled makes of the tiles' PCB1 containers."""
-    from . import container, tiles
+    from . import tiles
     qualities = [float(q) for q in qualities]
-    step = int(max_tiles_per_call)
-    if step < 1:
-        raise ValueError(f"max_tiles_per_call must be at least 1, got {max_tiles_per_call}")
-    x, g = cut_frame(planes, fmt, matrix, range, upsample, tile, overlap)
-    bufs = []
-    for a in _range(0, g.n, step):
-        datas = model.compress_levels(x[a:a + step], qualities, mask_pol=mask_pol)
-        strings = [d["strings"] for d in datas]
-        bufs += [container.pack(strings, datas[0]["shape"], qualities, image_size=(g.T, g.T), mask_pol=mask_pol, image_index=b)
-                 for b in _range(min(step, g.n - a))]
+    step = _tilecodec.tiles_per_call(max_tiles_per_call)
+    x, g = cut_frame(planes, fmt, matrix, range, upsample, tile, overlap)        # the whole frame in one launch
+    bufs = _tilecodec.encode_items(model, g.n, step, qualities, mask_pol, g.T, lambda a, b: x[a:a + b])
     return pack_frame_tiled(tiles.pack_tiled(bufs, g.H, g.W, g.T, g.O), fmt, matrix, range, upsample)
 
 
@@ -267,9 +253,7 @@ def decode_frame_tiled(model, buf, level=-1, region=None, fmt=None, max_tiles_pe
     is computed from the decoder's float output, not converted from codes).  Only the tiles that cover the region are read and
     decoded (max_tiles_per_call at a time, one batch each); every refusal is a ContainerError raised before the model is touched."""
     from . import container, tiles
-    step = int(max_tiles_per_call)
-    if step < 1:
-        raise ValueError(f"max_tiles_per_call must be at least 1, got {max_tiles_per_call}")
+    step = _tilecodec.tiles_per_call(max_tiles_per_call)
     hd = parse_frame_tiled(buf)
     out_fmt = hd["fmt"] if fmt is None else fmt
     _check_enums(out_fmt)

@@ -20,7 +20,7 @@ import ctypes as C
 import math
 import struct
 
-from . import _imagelib
+from . import _imagelib, _tilecodec
 from ._lib import PC_OK
 from .pixels import Geometry, padding
 
@@ -348,11 +348,7 @@ def parse_frame(buf):
     ver, f, m, r, u, bits, H, W = struct.unpack_from(_HEAD, buf, 4)
     if ver != VERSION:
         raise container.ContainerError(f"unsupported PCF1 version {ver}")
-    fi, mi, ri, ui = _inv(FORMATS), _inv(_MATRIX_ID), _inv(RANGES), _inv(UPSAMPLES)
-    if f not in fi or m not in mi or r not in ri or u not in ui:
-        raise container.ContainerError(f"corrupt PCF1 header: fmt {f}, matrix {m}, range {r}, upsample {u}")
-    if bits != bits_of(fi[f]):
-        raise container.ContainerError(f"corrupt PCF1 header: {bits} bits for {fi[f]!r}")
+    params = _tilecodec.frame_params(f, m, r, u, bits, "PCF1")
     if H < 1 or W < 1:
         raise container.ContainerError(f"corrupt PCF1 header: frame size {H}x{W}")
     blob = bytes(buf[HEADER_BYTES:])
@@ -362,7 +358,7 @@ def parse_frame(buf):
         raise container.ContainerError(f"PCF1: the PCB1 blob does not parse: {e}") from None
     if tuple(hd["image_size"]) != (H, W):
         raise container.ContainerError(f"PCF1 header says {H}x{W}, its PCB1 blob {hd['image_size'][0]}x{hd['image_size'][1]}")
-    return {"fmt": fi[f], "matrix": mi[m], "range": ri[r], "upsample": ui[u], "bits": bits, "H": H, "W": W, "blob": blob, "pcb1": hd}
+    return dict(params, H=H, W=W, blob=blob, pcb1=hd)
 
 
 def encode_frame(model, planes, qualities, fmt, matrix="bt709", range="limited", upsample="linear", mask_pol="point-based-std"):

@@ -22,10 +22,10 @@ import collections
 import ctypes as C
 from fractions import Fraction
 
-from . import _imagelib
+from . import _imagelib, _tilecodec
 from ._lib import PC_OK
 from .pixels import ROUNDINGS
-from .tiles import HEADER_BYTES, TileGrid, _check_tiles, _view3, grid_of, pack_tiled
+from .tiles import HEADER_BYTES, TileGrid, _check_tiles, _fit_tiles, _view3, grid_of, pack_tiled
 
 LIB_PATH = _imagelib.lib_path("rate")
 
@@ -88,8 +88,7 @@ def tile_distortion(x_hat_tiles, grid, ref, first_tile=0, ref_layout="hwc", roun
         rview = rview[:3] + (max(rview[3], g.W * (3 if ref_layout == "hwc" else 1)),)
     if x.device.type != "cuda":
         raise ValueError(f"x_hat_tiles must be on a GPU (there is no CPU fallback), got {x.device}")
-    if x.stride(3) != 1 or x.stride(2) < g.T or min(x.stride()[:2]) < 1:
-        x = x.contiguous()
+    x = _fit_tiles(x, g.T)
     L = lib()
     with torch.cuda.device(x.device):
         nbytes = L.pc_rate_workspace_size(g.T, n)
@@ -212,52 +211,35 @@ def encode_tiled_to_size(model, img, qualities, target_bytes, tile=512, overlap=
     (decompress_levels) and measured max_tiles_per_call at a time, so a call holds at most max_tiles_per_call * (1 + len(qualities))
     tile tensors on the device; neither the bytes nor the plan depend on it."""
     import torch
-    from . import container, tiles
-    qualities = [float(q) for q in qualities]
-    if not qualities:
-        raise ValueError("at least one level")
+    from . import tiles
+    qualities = _tilecodec.levels_of(qualities)
     if rounding not in ROUNDINGS:
         raise ValueError(f"rounding must be 'nearest' or 'trunc', got {rounding!r}")
-    step = int(max_tiles_per_call)
-    if step < 1:
-        raise ValueError(f"max_tiles_per_call must be at least 1, got {max_tiles_per_call}")
+    step = _tilecodec.tiles_per_call(max_tiles_per_call)
     target_bytes = int(target_bytes)
     t4, view, (H, W) = _view3(img, layout, "img")
     g = grid_of(H, W, tile, overlap)
     n = g.ny * g.nx
-    if importance is not None:
-        importance = list(importance)
-        if importance and isinstance(importance[0], (list, tuple)):
-            importance = [v for row in importance for v in row]
-        if len(importance) != n:
-            raise ValueError(f"importance needs one number per tile of the {g.ny}x{g.nx} grid, got {len(importance)}")
+    importance = _tilecodec.importance_of(importance, g)
     TL = tiles.lib()
-    bufs, rates, dists = [], [], []
-    for a in range(0, n, step):
-        b = min(step, n - a)
+
+    def cut(a, b):
         with torch.cuda.device(t4.device):
             x = torch.empty((b, 3, g.T, g.T), dtype=torch.float32, device=t4.device)
             k = 0
-            while k < b:                                                # the linear range a .. a + b - 1, one piece per grid row
-                i, j = divmod(a + k, g.nx)
-                m = min(b - k, g.nx - j)
+            for i, j, m in _tilecodec.row_pieces(a, b, g.nx):
                 rc = TL.pc_tiles_cut_u8(*view, H, W, g.T, g.O, i, j, 1, m, x[k:].data_ptr(), torch.cuda.current_stream(t4.device).cuda_stream)
                 if rc != PC_OK:
                     raise tiles.TilesError(rc, "pc_tiles_cut_u8")
                 k += m
-        datas = model.compress_levels(x, qualities, mask_pol=mask_pol)
-        del x
-        strings = [d["strings"] for d in datas]
-        shape = datas[0]["shape"]
-        decoded = model.decompress_levels(strings, shape, qualities, mask_pol)
+        return x
+
+    def measure(a, b, decoded):
         d = torch.stack([tile_distortion(o["x_hat"], g, t4[0], a, layout, rounding).sum(1) for o in decoded], 1).tolist()   # [b][levels]
-        del decoded
-        for k in range(b):
-            bufs.append([container.pack([strings[l]], shape, [q], image_size=(g.T, g.T), mask_pol=mask_pol, image_index=k)
-                         for l, q in enumerate(qualities)])
-            rates.append([TABLE_ENTRY_BYTES + len(p) for p in bufs[-1]])
-            dists.append([int(v) for v in d[k]])
+        return [[int(v) for v in row] for row in d]
+    bufs, dists = _tilecodec.encode_items(model, n, step, qualities, mask_pol, g.T, cut, measure)
     del t4
+    rates = [[TABLE_ENTRY_BYTES + len(p) for p in row] for row in bufs]
     levels = allocate(rates, dists, target_bytes - HEADER_BYTES, importance)
     buf = pack_tiled([bufs[t][levels[t]] for t in range(n)], g.H, g.W, g.T, g.O, per_tile_levels=True)
     return buf, RatePlan(levels, rates, dists, 2 * g.O if g.O else 1, len(buf), sum(dists[t][levels[t]] for t in range(n)))

@@ -40,7 +40,7 @@ import collections
 import ctypes as C
 import struct
 
-from . import _imagelib
+from . import _imagelib, _tilecodec
 from ._lib import PC_OK
 from .container import ContainerError
 from .pixels import LAYOUTS, ROUNDINGS, Distortion, _hw, _u8_view
@@ -183,6 +183,11 @@ def _check_tiles(x, g):
         raise ValueError(f"x_hat_tiles must be [{g.n},3,{g.T},{g.T}] for {g}, got {tuple(x.shape)}")
 
 
+def _fit_tiles(x, T):
+    """a tile tensor the kernels can take as it is, or its contiguous copy"""
+    return x if x.stride(3) == 1 and x.stride(2) >= T and min(x.stride()[:2]) >= 1 else x.contiguous()
+
+
 def stitch(x_hat_tiles, grid, window=None, layout="hwc", rounding="nearest", ref=None, ref_layout=None, image=True):
     """x_hat_tiles: float32 cuda [n,3,T,T], the decoded tiles of grid's rectangle (any tile / channel / row strides, unit stride along a
     row) -> uint8 [h,w,3] ("hwc") or [3,h,w] ("chw"): the window (y0, x0, h, w) of the image (default: all of it), every covering tile
@@ -217,8 +222,7 @@ def stitch(x_hat_tiles, grid, window=None, layout="hwc", rounding="nearest", ref
         rview = (rfull[0] + y0 * rfull[3] + px * x0, rfull[1], rfull[2], rfull[3])
     if x.device.type != "cuda":
         raise ValueError(f"x_hat_tiles must be on a GPU (there is no CPU fallback), got {x.device}")
-    if x.stride(3) != 1 or x.stride(2) < g.T or min(x.stride()[:2]) < 1:
-        x = x.contiguous()
+    x = _fit_tiles(x, g.T)
     L = lib()
     with torch.cuda.device(x.device):
         out, oview = None, (None, 0, 0, 0)
@@ -293,53 +297,23 @@ def parse_tiled(buf):
     ver, contract, H, W, T, O, ny, nx = struct.unpack_from(_HEAD, buf, 4)
     if ver != VERSION:
         raise ContainerError(f"unsupported version {ver}")
-    cy, cx = C.c_int(0), C.c_int(0)
-    if max(H, W, T, O) >= 1 << 31 or lib().pc_tiles_grid(H, W, T, O, C.byref(cy), C.byref(cx)) != PC_OK:
-        raise ContainerError(f"corrupt header: image {H}x{W}, tile {T}, overlap {O}")
-    if (cy.value, cx.value) != (ny, nx):
-        raise ContainerError(f"corrupt header: grid {ny}x{nx}, but a {H}x{W} image in tiles of {T} with overlap {O} has {cy.value}x{cx.value}")
-    g = grid_of(H, W, T, O)
-    if (g.ny, g.nx) != (ny, nx):
-        raise ContainerError("corrupt header: grid")
-    start = HEADER_BYTES + 16 * ny * nx
-    if len(buf) < start:
-        raise ContainerError("truncated tile table")
-    flat = struct.unpack_from(f"<{2 * ny * nx}Q", buf, HEADER_BYTES)
-    return {"magic": magic, "contract": contract, "grid": g, "table": list(zip(flat[0::2], flat[1::2])), "payload_start": start}
+    g, table, start = _tilecodec.tile_table(buf, HEADER_BYTES, H, W, T, O, ny, nx)
+    return {"magic": magic, "contract": contract, "grid": g, "table": table, "payload_start": start}
 
 
 def tile_bytes(buf, hd, t):
     """The PCB1 container of tile t, after checking its table entry against the buffer and its header against the grid."""
-    from . import container
-    off, n = hd["table"][t]
-    if off < hd["payload_start"] or off + n > len(buf):
-        raise ContainerError(f"tile {t}: table entry ({off}, {n}) points outside the {len(buf)} bytes at hand (truncated or corrupt)")
-    tb = bytes(buf[off:off + n])
-    th = container.parse_header(tb)
-    T = hd["grid"].T
-    if th["image_size"] != (T, T) or tuple(th["shape"]) != (T // 64, T // 64):
-        raise ContainerError(f"tile {t}: its container holds a {th['image_size'][0]}x{th['image_size'][1]} image, not a {T}x{T} tile")
-    if th["contract"] != hd["contract"]:
-        raise ContainerError(f"tile {t}: numeric contract 0x{th['contract']:08x}, the container's is 0x{hd['contract']:08x}")
-    return tb, th
+    return _tilecodec.entry_bytes(buf, hd, hd["table"][t], f"tile {t}")
 
 
 def encode_tiled(model, img, qualities, tile=512, overlap=0, mask_pol="point-based-std", layout="hwc", max_tiles_per_call=32):
     """uint8 cuda image [H,W,3] / [3,H,W] -> one PCT1 container (bytes) holding every level of `qualities` for every tile.  The tiles
     are coded max_tiles_per_call at a time as one batch each (model.compress_levels), which bounds the device memory a call needs
     whatever the image's size; the bytes do not depend on it.  model: a loaded ChannelProgresssiveWACNN (any topology / post-filter)."""
-    from . import container
     qualities = [float(q) for q in qualities]
-    step = int(max_tiles_per_call)
-    if step < 1:
-        raise ValueError(f"max_tiles_per_call must be at least 1, got {max_tiles_per_call}")
-    tiles, g = cut(img, tile, overlap, layout)
-    bufs = []
-    for a in range(0, g.n, step):
-        datas = model.compress_levels(tiles[a:a + step], qualities, mask_pol=mask_pol)
-        strings = [d["strings"] for d in datas]
-        bufs += [container.pack(strings, datas[0]["shape"], qualities, image_size=(g.T, g.T), mask_pol=mask_pol, image_index=b)
-                 for b in range(min(step, g.n - a))]
+    step = _tilecodec.tiles_per_call(max_tiles_per_call)
+    tiles, g = cut(img, tile, overlap, layout)                                   # the whole image in one launch
+    bufs = _tilecodec.encode_items(model, g.n, step, qualities, mask_pol, g.T, lambda a, b: tiles[a:a + b])
     return pack_tiled(bufs, g.H, g.W, g.T, g.O)
 
 
@@ -354,9 +328,7 @@ def decode_tiled(model, buf, level=-1, region=None, layout="hwc", rounding="near
         raise ValueError(f"layout must be 'hwc' or 'chw', got {layout!r}")
     if rounding not in ROUNDINGS:
         raise ValueError(f"rounding must be 'nearest' or 'trunc', got {rounding!r}")
-    step = int(max_tiles_per_call)
-    if step < 1:
-        raise ValueError(f"max_tiles_per_call must be at least 1, got {max_tiles_per_call}")
+    step = _tilecodec.tiles_per_call(max_tiles_per_call)
     x_hat, g, window = _decode_region_tiles(model, buf, level, region, step)
     return stitch(x_hat, g, window, layout=layout, rounding=rounding)
 
@@ -364,75 +336,27 @@ def decode_tiled(model, buf, level=-1, region=None, layout="hwc", rounding="near
 def _decode_region_tiles(model, buf, level, region, step):
     """What decode_tiled (and frame_tiles.decode_frame_tiled, on the PCT1 / PCT2 container inside a PCG1 one) does up to the stitch:
     one level of the tiles that cover region = (y0, x0, h, w) (None: the whole image) -> (x_hat float32 [n,3,T,T], the TileGrid whose
-    rectangle they are, the window as four ints), decoded step tiles at a time.  Every refusal is a ContainerError (a region outside
-    the image a ValueError) raised before the model is touched."""
-    import torch
-    from . import container
+    rectangle they are, the window as four ints), decoded step tiles at a time by _tilecodec.decode_positions: the tiles of a PCT1
+    container as one group in tile order, those of a PCT2 container (one level each) grouped by quality, ascending, tile order
+    within a group.  Every refusal -- a tile with another number of levels, tiles that differ in what a codec call shares -- is a
+    ContainerError (a region outside the image a ValueError) raised before the model is touched."""
     hd = parse_tiled(buf)
     pct2 = hd["magic"] == MAGIC2
-    if pct2 and int(level) not in (-1, 0):
-        raise ContainerError(f"a PCT2 container holds one level per tile: level must be -1 or 0, got {level}")
+    if pct2:
+        _tilecodec.one_level(level, "PCT2")
     g = hd["grid"]
     window = _window((0, 0, g.H, g.W) if region is None else region, g.H, g.W)
     g = g.with_rect(g.covering(window))
     blobs = [tile_bytes(buf, hd, (g.ty0 + a) * g.nx + g.tx0 + b) for a in range(g.nty) for b in range(g.ntx)]
-    if hd["contract"] != container.build_contract_id():
-        raise ContainerError(f"container was coded under numeric contract 0x{hd['contract']:08x}, this decoder implements "
-                             f"0x{container.build_contract_id():08x}: the streams are not interchangeable (DESIGN.md section 2)")
-    if pct2:
-        return _decode_per_tile_levels(model, blobs, g, step), g, window
-    per_tile, common = [], None
-    for k, (tb, th) in enumerate(blobs):
-        n = len(th["qualities"])
-        lv = int(level) + n if int(level) < 0 else int(level)
-        if not 0 <= lv < n:
-            raise ContainerError(f"no level {level} among {n}")
-        strings, shape, qs, _, mask_pol = container.unpack(tb, levels=[lv], expect_contract=False)      # checked above, once
-        key = (tuple(shape), qs[0], mask_pol, len(strings[0][0]))
-        if common is None:
-            common = key
-        elif key != common:
-            raise ContainerError(f"tile {k} of the region was coded as {key}, its first tile as {common}")
-        per_tile.append(strings[0])
-    shape, q, mask_pol, ns = common
-    outs = []
-    for a in range(0, g.n, step):
-        chunk = per_tile[a:a + step]
-        ys = [[s[0][k][0] for s in chunk] for k in range(ns)]              # y_strings[slice][image]
-        zs = [s[1][0] for s in chunk]
-        outs.append(model.decompress([ys, zs], shape, q, mask_pol)["x_hat"])
-    return (outs[0] if len(outs) == 1 else torch.cat(outs)), g, window
-
-
-def _decode_per_tile_levels(model, blobs, g, step):
-    """The tiles of a PCT2 region -> float32 [n,3,T,T]: every tile holds one level; the tiles are grouped by quality (ascending, tile
-    order within a group), each group is decoded step tiles at a time and scattered to the tiles' places.  ContainerError, before the
-    model is touched, for a tile with another number of levels and for tiles that differ in mask policy, latent shape or slices."""
-    import torch
-    from . import container
+    _tilecodec.check_contract(hd["contract"])
     per_tile, groups, common = [], {}, None
     for k, (tb, th) in enumerate(blobs):
-        if len(th["qualities"]) != 1:
+        if pct2 and len(th["qualities"]) != 1:
             raise ContainerError(f"tile {k} of the region holds {len(th['qualities'])} levels, a PCT2 tile holds exactly one")
-        strings, shape, qs, _, mask_pol = container.unpack(tb, levels=[0], expect_contract=False)       # checked by decode_tiled, once
-        key = (tuple(shape), mask_pol)
-        if common is None:
-            common = key
-        elif key != common:
-            raise ContainerError(f"tile {k} of the region was coded as {key}, its first tile as {common}")
-        per_tile.append(strings[0])
-        groups.setdefault(qs[0], []).append(k)
-    shape, mask_pol = common
-    x_hat = None
-    for q in sorted(groups):
-        idx = groups[q]
-        for a in range(0, len(idx), step):
-            part = idx[a:a + step]
-            chunk = [per_tile[k] for k in part]
-            ys = [[s[0][k][0] for s in chunk] for k in range(len(chunk[0][0]))]      # y_strings[slice][image]
-            zs = [s[1][0] for s in chunk]
-            out = model.decompress([ys, zs], shape, q, mask_pol)["x_hat"]
-            if x_hat is None:
-                x_hat = torch.empty((g.n,) + tuple(out.shape[1:]), dtype=out.dtype, device=out.device)
-            x_hat[torch.tensor(part, device=out.device)] = out
-    return x_hat
+        shape, q, mask_pol, strings = _tilecodec.level_strings(tb, th, 0 if pct2 else level)
+        key = (shape, mask_pol) if pct2 else (shape, q, mask_pol, len(strings[0]))
+        common = key if common is None else common
+        _tilecodec.same_coding(key, common, f"tile {k} of the region", "its first tile")
+        per_tile.append(strings)
+        groups.setdefault(q, []).append(k)
+    return _tilecodec.decode_positions(model, per_tile, sorted(groups.items()), shape, mask_pol, step, g.n), g, window
