@@ -22,8 +22,8 @@ tiles.decode_tiled of it gives the uint8 RGB rendering.
 
 There is no CPU fallback: CPU tensors raise ValueError before any device call.  Everything runs on the current stream of the tensor's
 device.  Rate control from YUV (a frame in at most N bytes, per-tile levels) is frame_rate.py's; sequences of frames (tiles of several
-frames in one codec call, static tiles coded once) are clips.py's.  Out of scope: 4:2:2 / 4:4:4 and other chroma sitings,
-compress_with_ac.
+frames in one codec call, static tiles coded once) are clips.py's; 4:2:2 / 4:4:4 and left- or top-left-sited chroma are
+chroma_tiles.py's.  Out of scope: compress_with_ac.
 """
 import ctypes as C
 import struct
