@@ -186,8 +186,9 @@ def decode_positions(model, strings_of, groups, shape, mask_pol, step, n, prev=N
 # -- argument checks ---------------------------------------------------------------------------------------------------------------------
 
 def max_tile(fmt):
-    """the largest tile whose distortion sums fit 63 bits: T^4 (2^n - 1)^2 < 2^60"""
-    return 1024 if fmt == "p010" else 2048
+    """the largest tile whose distortion sums fit 63 bits: T^4 (2^n - 1)^2 < 2^60; 1024 for the 10-bit formats of chroma.FORMATS"""
+    from .chroma import FORMATS
+    return 1024 if fmt in FORMATS and FORMATS[fmt].bits == 10 else 2048
 
 
 def tile_limit(T, fmt):

@@ -16,7 +16,8 @@ the quantiser, where they do.
 
 There is no CPU fallback: CPU tensors raise ValueError before any device call.  Everything runs on the current stream of the tensor's
 device.  Sequences of frames are clips.py's (without rate control) and clip_rate.py's (a clip in at most N bytes).  Out of scope: a
-target PSNR (the dual problem), 4:2:2 / 4:4:4 and other chroma sitings, perceptual metrics, compress_with_ac.
+target PSNR (the dual problem), perceptual metrics, compress_with_ac.  4:2:2 / 4:4:4 and left- / top-left-sited chroma are chroma_rate.py's
+(section 24), which computes these sums bit for bit for the three formats here.
 """
 import collections
 import ctypes as C
