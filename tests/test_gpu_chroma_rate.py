@@ -112,6 +112,28 @@ def test_the_other_sizes_overlaps_matrices_and_full_range(fmt):
     run_matrix(RS.other_cases(fmt))
 
 
+def band_cases():
+    """O = 24 (S = 40, den = 48: wide where the views allow it) and O = 28 (S = 36, den = 56: narrow at sx = 2, wide at 4:4:4) on
+    100 x 150: one format per kernel shape and element width, every siting, aligned and not.  Not part of tests/chroma_rate_cases.py's
+    ledger: no instantiation depends on them."""
+    shapes = [("nv12", "topleft"), ("p010", "centre"), ("nv16", "left"), ("i210", "centre"), ("i444", "left"), ("p410", "topleft")]
+    out = []
+    for n, ((fmt, siting), O) in enumerate((s, O) for s in shapes for O in (24, 28)):
+        matrix, rng = RS.OTHER_SETTINGS[n % len(RS.OTHER_SETTINGS)]
+        for aligned in (True, False):
+            out.append(RS.Case(fmt, matrix, rng, siting, 100, 150, O, 200 + n, *RS.layout_of(n, aligned)))
+    return out
+
+
+def test_overlaps_whose_band_quotients_are_no_floats():
+    """the sums weigh with the integer numerators 2u + 1, which are exact whatever 2 O is; what is new is the band geometry.  Every
+    case asserts the access path chroma_rate_cases.wide predicts."""
+    cases = band_cases()
+    assert {RS.wide(c) for c in cases if c.O == 24} == {True, False}
+    assert {(RS.wide(c), CC.sub(c.fmt)[0]) for c in cases if c.O == 28} == {(False, 2), (True, 1), (False, 1)}
+    run_matrix(cases)
+
+
 # -- 2. both paths on the same data --------------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("fmt,siting", [("nv16", "left"), ("p210", "topleft"), ("i444", "centre"), ("nv12", "topleft"), ("i010", "left")])

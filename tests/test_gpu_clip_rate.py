@@ -28,6 +28,7 @@ POL = "point-based-std"
 T = 64
 SIZES = [(1, 1), (65, 63), (100, 150), (127, 129)]
 OVERLAPS = [0, 4, 16, 32]
+BAND_OVERLAPS = [24, 28]                                                    # 2 O is no power of two (tests/band_cases.py)
 MATS = list(FC.MATRICES)
 #: the three frames of a table as views: all aligned with row strides that are multiples of 4 (the wide path's), or pitched
 #: differently with one of them one element past an allocation start (narrow, whichever frame a job names)
@@ -75,8 +76,7 @@ def job_list(n, seed):
     return jobs
 
 
-@pytest.mark.parametrize("hw", SIZES)
-def test_kernel_matrix_exact_on_both_paths(hw):
+def kernel_matrix(hw, overlaps):
     """every overlap x format x range against the restatement and against frame_tile_distortion of the same tile and frame; a table
     of three frames with different contents, once all aligned (wide where the floats and the overlap allow it) and once with mixed
     pitches and an offset pointer (narrow); the jobs out of frame order, with a repeat, covering every tile of one frame; the Python
@@ -85,7 +85,7 @@ def test_kernel_matrix_exact_on_both_paths(hw):
     from progressivecodec_amd import frame_rate
     H, W = hw
     seen = set()
-    for O in OVERLAPS:
+    for O in overlaps:
         ny, nx = TC.grid(H, W, T, O)
         n = ny * nx
         jobs = job_list(n, H + W + O)
@@ -135,6 +135,17 @@ def test_kernel_matrix_exact_on_both_paths(hw):
                     side.synchronize()
                     assert got_s.tolist() == want[-2:]
     assert seen == {True, False}
+
+
+@pytest.mark.parametrize("hw", SIZES)
+def test_kernel_matrix_exact_on_both_paths(hw):
+    kernel_matrix(hw, OVERLAPS)
+
+
+def test_kernel_matrix_at_overlaps_whose_band_quotients_are_no_floats():
+    """O = 24 (S = 40, den = 48: the wide path where there is one) and O = 28 (S = 36, den = 56: narrow at 4:2:0) on one picture.  The
+    sums weigh with the integer numerators 2u + 1, which are exact whatever 2 O is; what is new is the band geometry."""
+    kernel_matrix((100, 150), BAND_OVERLAPS)
 
 
 @pytest.mark.parametrize("fmt", ["nv12", "i420", "p010"])

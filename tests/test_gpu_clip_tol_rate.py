@@ -31,6 +31,7 @@ POL = "point-based-std"
 T = 64
 SIZES = [(65, 63), (100, 150), (127, 129)]
 OVERLAPS = [0, 4, 16, 32]
+BAND_OVERLAPS = [24, 28]                                                    # 2 O is no power of two (tests/band_cases.py)
 MATS = list(FC.MATRICES)
 
 
@@ -97,15 +98,14 @@ def expanded_on_the_gpu(x, g, planes, tile_ids, runs, fmt, matrix, rng):
     return CR().tile_distortion_jobs(rep, g, planes, jobs, fmt, matrix, rng).tolist()
 
 
-@pytest.mark.parametrize("hw", SIZES)
-def test_kernel_matrix_exact_on_both_paths(hw):
+def kernel_matrix(hw, overlaps):
     """every overlap x format x range against the restatement and against clip_rate.tile_distortion_jobs of the expanded job list; a
     table of three frames with different contents, once all aligned (wide where the floats and the overlap allow it) and once with
     mixed pitches and an offset pointer (narrow); the Python call on a list, on batched planes and on a side stream."""
     ctr = CTR()
     H, W = hw
     seen = set()
-    for O in OVERLAPS:
+    for O in overlaps:
         ny, nx = TC.grid(H, W, T, O)
         n = ny * nx
         tile_ids, runs = run_list(n, H + W + O)
@@ -155,6 +155,17 @@ def test_kernel_matrix_exact_on_both_paths(hw):
                     side.synchronize()
                     assert got_s.tolist() == want[off[-3]:]
     assert seen == {True, False}
+
+
+@pytest.mark.parametrize("hw", SIZES)
+def test_kernel_matrix_exact_on_both_paths(hw):
+    kernel_matrix(hw, OVERLAPS)
+
+
+def test_kernel_matrix_at_overlaps_whose_band_quotients_are_no_floats():
+    """O = 24 (S = 40, den = 48: the wide path where there is one) and O = 28 (S = 36, den = 56: narrow at 4:2:0) on one picture.  The
+    sums weigh with the integer numerators 2u + 1, which are exact whatever 2 O is; what is new is the band geometry."""
+    kernel_matrix((100, 150), BAND_OVERLAPS)
 
 
 @pytest.mark.parametrize("fmt", ["nv12", "p010"])

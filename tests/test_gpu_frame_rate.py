@@ -26,6 +26,7 @@ POL = "point-based-std"
 T = 64
 SIZES = [(1, 1), (2, 2), (64, 64), (65, 63), (100, 150), (127, 129)]
 OVERLAPS = [0, 4, 16, 32]
+BAND_OVERLAPS = [24, 28]                                                    # 2 O is no power of two (tests/band_cases.py)
 MATS = list(FC.MATRICES)
 #: the reference planes: aligned with strides that are multiples of 4; pitched with a stride that is none; offset by one element
 REF_VIEWS = [("pad4", 0), ("loose", 0), ("pad4", 1)]
@@ -73,15 +74,14 @@ def sse_raw(x, H, W, O, first, fmt, rng, matrix, ref, size=T, nbytes=None, strid
     return rc, buf, bool(h[-1] == POISON64 and ((h[:-1] != POISON64).all() if rc == 0 else (h == POISON64).all()))
 
 
-@pytest.mark.parametrize("hw", SIZES)
-def test_kernel_matrix_exact_on_both_paths(hw):
+def kernel_matrix(hw, overlaps):
     """every overlap x format x range against the restatement; tiles contiguous and one float past an allocation start; reference
     planes aligned, pitched and offset by one element; sub-ranges and every tile alone; the Python call, on a side stream and on views
     it has to copy.  Wide exactly where pc_frame_rate_plan's preconditions hold."""
     fq = FQ()
     H, W = hw
     seen = set()
-    for O in OVERLAPS:
+    for O in overlaps:
         ny, nx = TC.grid(H, W, T, O)
         n = ny * nx
         x_np = TC.hostile_tiles(n, T, seed=H + W + O)
@@ -132,6 +132,17 @@ def test_kernel_matrix_exact_on_both_paths(hw):
                     side.synchronize()
                     assert got_s.tolist() == want[n - 1:]
     assert seen == {True, False}
+
+
+@pytest.mark.parametrize("hw", SIZES)
+def test_kernel_matrix_exact_on_both_paths(hw):
+    kernel_matrix(hw, OVERLAPS)
+
+
+def test_kernel_matrix_at_overlaps_whose_band_quotients_are_no_floats():
+    """O = 24 (S = 40, den = 48: the wide path where there is one) and O = 28 (S = 36, den = 56: narrow at 4:2:0) on one picture.  The
+    sums weigh with the integer numerators 2u + 1, which are exact whatever 2 O is; what is new is the band geometry."""
+    kernel_matrix((100, 150), BAND_OVERLAPS)
 
 
 def saturated(H, W, fmt):

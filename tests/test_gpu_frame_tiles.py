@@ -142,7 +142,7 @@ def window_frame(f, fmt, win):
     return FC.frame(*GC.crop_codes(FC.codes(f, fmt), win), fmt)
 
 
-def stitch_raw(xv, fmt, matrix, rng, H, W, O, rect, win, dst_views, ref_views, nbytes=None):
+def stitch_raw(xv, fmt, matrix, rng, H, W, O, rect, win, dst_views, ref_views, nbytes=None, T=T):
     """pc_frame_tiles_stitch -> (status, wide, the [3,3] sums buffer whose middle row is `sse`, poisoned beforehand, the workspace
     with one more word than needed)"""
     from progressivecodec_amd import frames

@@ -20,6 +20,7 @@ POL = "point-based-std"
 T = 64
 SIZES = [(1, 1), (64, 64), (65, 63), (100, 150), (127, 129)]
 OVERLAPS = [0, 4, 16, 32]
+BAND_OVERLAPS = [24, 28]                                                    # 2 O is no power of two (tests/band_cases.py)
 POISON = 0xA5
 POISON64 = -0x5A5A5A5A5A5A5A5B
 
@@ -112,14 +113,13 @@ def check_out(buf, want, case):
 REF_VIEWS = [(0, False, False), (0, False, True), (0, True, False), (1, False, True), (2, False, True), (3, False, True)]
 
 
-@pytest.mark.parametrize("hw", SIZES)
-def test_kernel_matrix_exact_on_both_paths(hw):
+def kernel_matrix(hw, overlaps):
     rate = RT()
     L = rate.lib()
     H, W = hw
     ref_chw = image(H, W, seed=7)
     seen = set()
-    for O in OVERLAPS:
+    for O in overlaps:
         ny, nx = TC.grid(H, W, T, O)
         n = ny * nx
         x_np = TC.hostile_tiles(n, T, seed=H + W + O)
@@ -164,6 +164,17 @@ def test_kernel_matrix_exact_on_both_paths(hw):
             else:
                 assert rate.tile_distortion(xs["odd"], rate.grid_of(H, W, T, O), refs[("hwc", REF_VIEWS[3])], rounding="trunc").tolist() == want
     assert seen == {True, False}
+
+
+@pytest.mark.parametrize("hw", SIZES)
+def test_kernel_matrix_exact_on_both_paths(hw):
+    kernel_matrix(hw, OVERLAPS)
+
+
+def test_kernel_matrix_at_overlaps_whose_band_quotients_are_no_floats():
+    """O = 24 (S = 40, den = 48: the wide path where there is one) and O = 28 (S = 36, den = 56: narrow at 4:2:0) on one picture.  The
+    sums weigh with the integer numerators 2u + 1, which are exact whatever 2 O is; what is new is the band geometry."""
+    kernel_matrix((100, 150), BAND_OVERLAPS)
 
 
 def test_the_largest_weights_meet_the_largest_error():

@@ -165,7 +165,7 @@ def float_tiles(x_np, variant):
     t = torch.from_numpy(x_np).to(DEV)
     if variant == "contiguous":
         return t
-    n = x_np.shape[0]
+    n, T = x_np.shape[0], x_np.shape[3]
     sh, off = (T + 4, 0) if variant == "loose4" else (T + 1, 1)
     sc = T * sh + (8 if variant == "loose4" else 3)
     st = 3 * sc + (4 if variant == "loose4" else 2)
@@ -192,7 +192,7 @@ def window_of(t, layout, win):
     return t[y0:y0 + h, x0:x0 + w, :] if layout == "hwc" else t[:, y0:y0 + h, x0:x0 + w]
 
 
-def stitch_raw(L, x, H, W, O, rect, win, rounding, dst, dst_layout, ref, ref_layout):
+def stitch_raw(L, x, H, W, O, rect, win, rounding, dst, dst_layout, ref, ref_layout, T=T):
     y0, x0, h, w = win
     sums = torch.full((2, 3), -1, dtype=torch.int64, device=DEV)
     nbytes = L.pc_tiles_stitch_workspace_size(x0, h, w)

@@ -84,6 +84,11 @@ def fmaf(a, b, c):
     return s.astype(np.float32)
 
 
+def product(wy, wx):
+    """float32 [h,w]: a pixel's weight for a tile, the one rounded float32 product wy * wx of its two axis weights"""
+    return (wy[:, None] * wx[None, :]).astype(np.float32)
+
+
 def blend(tiles, H, W, T, O, rect=None, window=None):
     """float32 [3,h,w]: m = fmaf(w_t, clamp01(x_t), acc) chained from +0.0 over the covering tiles in ascending tile index"""
     ny, nx = grid(H, W, T, O)
@@ -107,7 +112,7 @@ def blend(tiles, H, W, T, O, rect=None, window=None):
             if not (ty0 <= i < ty0 + nty and tx0 <= j < tx0 + ntx):
                 raise ValueError(f"tile {(i, j)} covers the window and is not in the rectangle")
             wx = weights(j, nx, T, O)[:xs.stop - xs.start]
-            wt = (wy[:, None] * wx[None, :]).astype(np.float32)
+            wt = product(wy, wx)
             c = K.clamp01(tiles[(i - ty0) * ntx + (j - tx0), :, :ys.stop - ys.start, :xs.stop - xs.start])
             acc[:, ys, xs] = fmaf(wt[None], c, acc[:, ys, xs])
     return acc[:, y0:y0 + h, x0:x0 + w]
