@@ -31,7 +31,7 @@ and bits as one byte each (PCH1's ids) -- 15 bytes -- then one PCT1 or PCT2 cont
 table offsets stay relative to its own start), so that tiles.decode_tiled of it gives the uint8 RGB rendering.
 
 There is no CPU fallback: CPU tensors raise ValueError before any device call.  Everything runs on the current stream of the tensor's
-device.  Out of scope: rate control and clips on these formats (the layers after this one, as sections 16 and 17 follow section 14).
+device.  Rate control on these formats is chroma_rate.py's (section 24), clips of them chroma_clips.py's (section 25).
 """
 import ctypes as C
 import struct

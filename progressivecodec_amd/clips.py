@@ -31,7 +31,8 @@ is asked for, so a clip cut off inside its payload still gives every frame whose
 There is no CPU fallback: CPU tensors raise ValueError before any device call.  Everything runs on the current stream of the tensors'
 device.  A tolerance (near-static tiles reused under an exact error bound) is clip_tol.py's, which produces this module's container.
 Out of scope: any inter-frame prediction, matching a tile against anything but the same tile of an earlier frame, rate control over
-a clip (clip_rate.py), 4:2:2 / 4:4:4, compress_with_ac.
+a clip (clip_rate.py), compress_with_ac.  4:2:2 / 4:4:4 and left- / top-left-sited chroma: chroma_clips.py, which is this module for
+the twelve formats and three sitings of chroma.py and shares this module's decode loop.
 """
 import collections
 import ctypes as C
@@ -94,21 +95,21 @@ def _grid(H, W, tile, overlap):
     return g
 
 
-def _clip_frames(frames, fmt, what="frames"):
+def _clip_frames(frames, fmt, what="frames", view=None, one=None):
     """a clip -> ([the planes of frame k as batched views [1,...], ...], H, W): a list of frames of one size on one device, or one
     tuple of batched planes, taken through their batch stride without a copy (frames._frame_view copies a plane only where its
-    innermost strides do not fit)"""
+    innermost strides do not fit).  view, one: another module's _frame_view and _one_frame (chroma_clips.py: the twelve formats)"""
     import torch
     if isinstance(frames, (tuple, list)) and frames and torch.is_tensor(frames[0]):
         if frames[0].dim() == 2:
             raise ValueError(f"{what} must be a list of frames or batched planes [F,H,W], got one frame")
-        ts, B, H, W, _ = _frame_view(frames, fmt, what)
+        ts, B, H, W, _ = (view or _frame_view)(frames, fmt, what)
         return [[t[k:k + 1] for t in ts] for k in _range(B)], H, W
     if not isinstance(frames, (tuple, list)) or not frames:
         raise ValueError(f"{what} must be a non-empty list of frames or a tuple of batched planes")
     out, size = [], None
     for k, f in enumerate(frames):
-        ts, H, W = _one_frame(f, fmt, f"{what}[{k}]")
+        ts, H, W = (one or _one_frame)(f, fmt, f"{what}[{k}]")
         if size is None:
             size = (H, W, ts[0].device)
         elif size != (H, W, ts[0].device):
@@ -266,6 +267,15 @@ def pack_clip(blobs, source, H, W, tile, overlap, fmt, matrix, range, upsample, 
     from . import container
     _check_enums(fmt, matrix, range, upsample)
     g = grid_of(H, W, tile, overlap)
+    F = _check_source(blobs, source, g)
+    contract = container.build_contract_id() if contract is None else int(contract)
+    head = MAGIC + struct.pack(_HEAD, VERSION, FORMATS[fmt], _MATRIX_ID[matrix], RANGES[range], UPSAMPLES[upsample], bits_of(fmt), contract,
+                               g.H, g.W, g.T, g.O, g.ny, g.nx, F)
+    return head + _table_and_payload(len(head), blobs, source)
+
+
+def _check_source(blobs, source, g):
+    """what pack_clip asks of blobs and source for the grid g -> the number of frames"""
     n, F = g.ny * g.nx, len(source)
     if F < 1 or F >= 1 << 32 or len(blobs) != F or any(len(r) != n for r in source) or any(len(r) != n for r in blobs):
         raise ContainerError(f"blobs and source must be [F][{n}] for the {g.ny}x{g.nx} grid, F >= 1")
@@ -273,10 +283,14 @@ def pack_clip(blobs, source, H, W, tile, overlap, fmt, matrix, range, upsample, 
         for t, s in enumerate(row):
             if s != f and (f == 0 or s != source[f - 1][t]):
                 raise ContainerError(f"source[{f}][{t}] = {s!r}: a tile is coded in its own frame or repeats the frame before it")
-    contract = container.build_contract_id() if contract is None else int(contract)
-    head = MAGIC + struct.pack(_HEAD, VERSION, FORMATS[fmt], _MATRIX_ID[matrix], RANGES[range], UPSAMPLES[upsample], bits_of(fmt), contract,
-                               g.H, g.W, g.T, g.O, g.ny, g.nx, F)
-    off = len(head) + ENTRY_BYTES * F * n
+    return F
+
+
+def _table_and_payload(head_bytes, blobs, source):
+    """the table and the payload behind a header of head_bytes bytes (PCS1's, or chroma_clips.py's PCL1): the coded tiles' blobs in
+    (frame, tile) order, a reused tile repeating the entry of the frame it was last coded in"""
+    F, n = len(source), len(source[0])
+    off = head_bytes + ENTRY_BYTES * F * n
     entries, table, payload = [], [], []
     for f, row in enumerate(source):
         cur = []
@@ -290,7 +304,16 @@ def pack_clip(blobs, source, H, W, tile, overlap, fmt, matrix, range, upsample, 
                 cur.append(entries[f - 1][t])
         entries.append(cur)
         table += [struct.pack("<QQ", *e) for e in cur]
-    return head + b"".join(table) + b"".join(payload)
+    return b"".join(table) + b"".join(payload)
+
+
+def _equal_or_disjoint(pairs, name):
+    """two table entries of the container `name` are either equal or disjoint"""
+    end = 0
+    for off, ln in sorted(set(pairs)):
+        if off < end:
+            raise ContainerError(f"corrupt {name} table: the entry ({off}, {ln}) overlaps another without being equal to it")
+        end = max(end, off + ln)
 
 
 def _parse(buf, magic):
@@ -305,11 +328,7 @@ def _parse(buf, magic):
         raise ContainerError(f"unsupported {name} version {ver}")
     params = _tilecodec.frame_params(f, m, r, u, bits, name)
     g, pairs, start = _tilecodec.tile_table(buf, HEADER_BYTES, H, W, T, O, ny, nx, F, f"{name} header", "frame", f"{name} table")
-    end = 0
-    for off, ln in sorted(set(pairs)):
-        if off < end:
-            raise ContainerError(f"corrupt {name} table: the entry ({off}, {ln}) overlaps another without being equal to it")
-        end = max(end, off + ln)
+    _equal_or_disjoint(pairs, name)
     n = ny * nx
     return dict(params, contract=contract, grid=g, F=F, table=[pairs[k * n:(k + 1) * n] for k in _range(F)], payload_start=start)
 
@@ -422,22 +441,26 @@ def encode_clip(model, frames, qualities, fmt, matrix="bt709", range="limited", 
     return buf, ClipPlan(source, n_coded, F * n - n_coded, len(buf))
 
 
-def _decode(model, buf, hd, one_level, frames, level, region, fmt, step, stitch):
+def _decode(model, buf, hd, one_level, frames, level, region, fmt, step, stitch, window_of=None, covering_of=None):
     """decode_clip on a parsed header: of a PCS1 container (one level of tiles that hold several), or with one_level of a PCS2
     container (clip_rate.decode_clip: the one level every tile holds; tiles may differ in quality).  All byte work comes first, and
-    every refusal is a ContainerError raised before the model is touched.  stitch is the caller's stitch_frame."""
+    every refusal is a ContainerError raised before the model is touched.  stitch is the caller's stitch_frame.  The two hooks are
+    for a caller whose formats have another window rule (chroma_clips.py, which has checked its output format itself):
+    window_of(region, H, W, out_fmt) -> the admissible window or ValueError, covering_of(grid, window, out_fmt) -> the rectangle of
+    tiles to read; by default the 4:2:0 check and the tiles that cover the window."""
     out_fmt = hd["fmt"] if fmt is None else fmt
-    _check_enums(out_fmt)
+    if window_of is None:
+        _check_enums(out_fmt)
     g = hd["grid"]
     try:
-        window = _admissible_window(region, g.H, g.W)
+        window = _admissible_window(region, g.H, g.W) if window_of is None else window_of(region, g.H, g.W, out_fmt)
     except ValueError as e:
         raise ContainerError(str(e)) from None
     try:
         wanted = list(_range(hd["F"])) if frames is None else [_frame_index(hd, k) for k in frames]
     except TypeError:
         raise ContainerError(f"frames must be an iterable of frame indices, got {frames!r}") from None
-    g = g.with_rect(g.covering(window))
+    g = g.with_rect(g.covering(window) if covering_of is None else covering_of(g, window, out_fmt))
     need = [(g.ty0 + a) * g.nx + g.tx0 + b for a in _range(g.nty) for b in _range(g.ntx)]
     # per requested frame the tiles it takes from the frame handled just before it and, of the rest, the strings by quality (one
     # quality where the tiles hold several levels: it is part of what they must share).  Under one_level, what a frame's tiles
