@@ -115,8 +115,10 @@ def changes_raw(cur, prev, fmt, siting, up, H, W, O, first, n, nbytes=None, size
     f = dict(chroma.FORMATS[fmt]._asdict(), hsite=chroma.SITINGS[siting][0], vsite=chroma.SITINGS[siting][1], up=frames.UPSAMPLES.get(up, up))
     f.update({k: v for k, v in raw.items() if k in f})
     buf = torch.full((max(n, 0) + 2, 3), POISON64, dtype=torch.int64, device=DEV)
-    need = L.pc_chroma_clips_changes_workspace_size(T, chroma.FORMATS[fmt].sy, max(n, 1))
-    ws = torch.full((need // 8 + 1,), POISON64, dtype=torch.int64, device=DEV)
+    # the workspace of the tile size the call is made with; of the module's where the library has none for it (a call to be refused)
+    need = (L.pc_chroma_clips_changes_workspace_size(size, chroma.FORMATS[fmt].sy, max(n, 1))
+            or L.pc_chroma_clips_changes_workspace_size(T, chroma.FORMATS[fmt].sy, max(n, 1)))
+    ws =torch.full((need // 8 + 1,), POISON64, dtype=torch.int64, device=DEV)
     a, b = frames._frame_struct(list(cur)), frames._frame_struct(list(prev))
     rc = L.pc_chroma_clips_tile_changes(C.byref(a) if not raw.get("no_cur") else None, C.byref(b) if not raw.get("no_prev") else None, *f.values(),
                                         H, W, size, O, first, n, ws.data_ptr() if not raw.get("no_ws") else None,
