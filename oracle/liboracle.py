@@ -58,6 +58,7 @@ def lib():
                                     _f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
         L.orc_win_attention.argtypes = [_f32p, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                         C.c_float, _f32p]
+        L.orc_win_attention_variant.argtypes = L.orc_win_attention.argtypes + [C.c_int]
         L.orc_msssim.argtypes = [_f32p, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, C.c_float, C.c_float,
                                  C.c_int, _f32p, C.c_int, C.c_int, _f32p, _f64p, _f32p, _f32p, _f64p, _f64p]
         L.orc_msssim.restype = C.c_int
@@ -171,13 +172,18 @@ def conv_nhwc(x, w, taps, stride, Ho, Wo, out=None, out_hw=None, ostride=(1, 1),
     return out
 
 
-def win_attention(qkv, bias, heads, ws, shift, scale):
+def win_attention(qkv, bias, heads, ws, shift, scale, variant=0):
+    """variant (tests of the tests only): 1 = exp(s - max) without pc_expf's exact zero below -87"""
     qkv = _c(qkv, np.float32)
     B, H, W, C3 = qkv.shape
     Cc = C3 // 3
     out = np.empty((B, H, W, Cc), np.float32)
-    lib().orc_win_attention(qkv.reshape(-1), _c(bias, np.float32).reshape(-1), B, H, W, Cc, heads, ws, shift,
-                            np.float32(scale), out.reshape(-1))
+    if variant:
+        lib().orc_win_attention_variant(qkv.reshape(-1), _c(bias, np.float32).reshape(-1), B, H, W, Cc, heads, ws, shift,
+                                        np.float32(scale), out.reshape(-1), variant)
+    else:
+        lib().orc_win_attention(qkv.reshape(-1), _c(bias, np.float32).reshape(-1), B, H, W, Cc, heads, ws, shift,
+                                np.float32(scale), out.reshape(-1))
     return out
 
 

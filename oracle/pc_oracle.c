@@ -249,12 +249,22 @@ ORC_API void orc_mask_point_based_std(const float *scale, int B, int64_t n_per, 
 }
 
 /* EntropyModel.quantize(..., "symbols", means): entropy_models.py:137-150
- * (x - mu, torch.round = half to even, .int()). mu may be NULL. */
+ * (x - mu, torch.round = half to even, .int()). mu may be NULL.
+ * The conversion to int32 is the contract's ("values outside the ordinary"): the rounded value is clipped to
+ * [INT32_MIN, INT32_MAX] and NaN gives 0 -- what the device conversion does; the plain C cast is undefined there. */
+static int32_t orc_to_sym(float r)
+{
+    if (r != r) return 0;
+    if (r >= 2147483648.0f) return INT32_MAX;
+    if (r <= -2147483648.0f) return INT32_MIN;
+    return (int32_t)r;
+}
+
 ORC_API void orc_quantize(const float *x, const float *mu, int64_t n, int32_t *sym)
 {
     for (int64_t i = 0; i < n; ++i) {
         const float d = mu ? x[i] - mu[i] : x[i];
-        sym[i] = (int32_t)pc_roundevenf(d);
+        sym[i] = orc_to_sym(pc_roundevenf(d));
     }
 }
 
@@ -376,8 +386,15 @@ ORC_API void orc_conv_nhwc(const float *x, int B, int H, int W, int Cin, int ldx
  * (roll(-s) :180, partition :185, reverse :193, roll(+s) :197 are index maps only).
  * Per (window, head, query i): s_j = fmaf-chain_e (q_i[e]*scale)*k_j[e]; s_j += bias; s_j += mask(0/-100)
  * (:164-175, only when shift > 0); p = exp(s - max) / sum (sum in ascending j); o[e] = fmaf-chain_j p_j*v_j[e]. */
-ORC_API void orc_win_attention(const float *qkv, const float *bias, int B, int H, int W, int C,
-                               int heads, int ws, int shift, float scale, float *out)
+/* variant (tests of the tests only): bit 0 evaluates exp(s - max) without pc_expf's exact zero below -87 (the double exp, rounded). */
+static float att_exp(float x, int variant)
+{
+    if ((variant & 1) && !(x > -87.0f) && x == x) return (float)exp((double)x);
+    return pc_expf(x);
+}
+
+static void win_attention(const float *qkv, const float *bias, int B, int H, int W, int C,
+                          int heads, int ws, int shift, float scale, float *out, int variant)
 {
     const int T = ws * ws, d = C / heads, nwy = H / ws, nwx = W / ws;
     const int64_t nwin = (int64_t)B * nwy * nwx;
@@ -409,7 +426,7 @@ ORC_API void orc_win_attention(const float *qkv, const float *bias, int B, int H
                     m = acc > m ? acc : m;
                 }
                 float sum = 0.0f;
-                for (int j = 0; j < T; ++j) { s[j] = pc_expf(s[j] - m); sum = sum + s[j]; }
+                for (int j = 0; j < T; ++j) { s[j] = att_exp(s[j] - m, variant); sum = sum + s[j]; }
                 for (int j = 0; j < T; ++j) s[j] = s[j] / sum;
                 float *o = out + pix[i] * C + h * d;
                 for (int e = 0; e < d; ++e) {
@@ -420,6 +437,18 @@ ORC_API void orc_win_attention(const float *qkv, const float *bias, int B, int H
             }
         }
     }
+}
+
+ORC_API void orc_win_attention(const float *qkv, const float *bias, int B, int H, int W, int C,
+                               int heads, int ws, int shift, float scale, float *out)
+{
+    win_attention(qkv, bias, B, H, W, C, heads, ws, shift, scale, out, 0);
+}
+
+ORC_API void orc_win_attention_variant(const float *qkv, const float *bias, int B, int H, int W, int C,
+                                       int heads, int ws, int shift, float scale, float *out, int variant)
+{
+    win_attention(qkv, bias, B, H, W, C, heads, ws, shift, scale, out, variant);
 }
 
 /* ------------------------------------------------------------------------- */

@@ -17,6 +17,7 @@ A case is a plain dict (see `case()`): the input segments, the geometry (kind 0 
   aux operand) moves an output by O(|x| |w|), orders of magnitude above the bound.
 
 `mutate` names one deliberate mistake of the restatement; tests/test_conv_contract_host.py checks that each one leaves the bound.
+tests/hostile_values.py is the table of the same shapes on operands outside the ordinary (subnormal, non-finite, overflowing chains).
 """
 import zlib
 
@@ -374,6 +375,26 @@ def within(c, got, d, group=0):
     bad = ~(diff <= bound)
     ratio = float(np.max(np.where(np.isfinite(diff), diff / bound, np.inf)))
     return not bad.any(), ratio, int(bad.sum())
+
+
+FLT_MIN, FLT_MAX = 2.0 ** -126, float(np.finfo(np.float32).max)
+
+
+def within_normal(c, got, d, group=0, exclude=None):
+    """`within` for operands outside the ordinary (tests/hostile_values.py): the same reference and the same bound, asserted on the
+    outputs whose float64 value is finite and of normal range and whose bound is finite and below FLT_MAX * 2^-24 (a chain whose
+    |x| |w| sum passes FLT_MAX may overflow in float32 where float64 does not: the bound does not cover that), less the outputs of
+    `exclude` (hostile_values.bound_exclusions).
+    (ok, worst ratio, count outside the bound, count of outputs judged)"""
+    with np.errstate(all="ignore"):
+        ref, bound = reference64(c, d, group)
+        judged = np.isfinite(ref) & (np.abs(ref) >= FLT_MIN) & (np.abs(ref) <= FLT_MAX) & np.isfinite(bound) & (bound < FLT_MAX * U)
+        if exclude is not None:
+            judged &= ~np.broadcast_to(exclude, judged.shape)
+        diff = np.abs(np.asarray(got, np.float64) - ref)
+        bad = judged & ~(diff <= bound)
+        ratio = float(np.max(np.where(judged, np.where(np.isfinite(diff), diff / bound, np.inf), 0.0))) if judged.any() else 0.0
+    return not bad.any(), ratio, int(bad.sum()), int(judged.sum())
 
 
 # ---------------------------------------------------------------------------------------------------------------- the matrix

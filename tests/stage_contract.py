@@ -119,6 +119,21 @@ def _rnd(x64):
     return np.where(rep, 0.0, U * np.abs(x64))
 
 
+def to_sym(v, mutate=None):
+    """(int32_t)pc_roundevenf(v) as the contract fixes it outside the finite |v| < 2^31 ("values outside the
+    ordinary"): round half to even in float32 (the identity from 2^23 on), clip to [-2^31, 2^31 - 1], then cast; NaN gives 0.  The
+    mutation "wrapping" is the other conversion in use: the low 32 bits of the integer (INT32_MIN for what no int64 holds)."""
+    v = np.asarray(v, F32)
+    with np.errstate(invalid="ignore"):
+        r = np.rint(v).astype(np.float64)
+    if mutate == "wrapping":
+        big = ~(np.abs(r) < 2.0 ** 63)                      # NaN included
+        i = np.where(big, 0.0, r).astype(np.int64)
+        return np.where(big, np.int64(-2 ** 31), ((i + 2 ** 31) % 2 ** 32) - 2 ** 31).astype(np.int32)
+    r = np.where(np.isnan(r), 0.0, r)
+    return np.clip(r, -2.0 ** 31, 2.0 ** 31 - 1).astype(np.int64).astype(np.int32)
+
+
 def _few_planted(n):
     """the N_PLANTED inexact ties count against the exclusion cap: planted only where the cap has room for them"""
     return n < 10 ** 4 or int(1e-4 * n) > 2 * N_PLANTED
@@ -289,7 +304,7 @@ def prep_restate(c, d, mutate=None):
     if mutate == "round_away":
         sym = (np.sign(v) * np.floor(np.abs(v) + F32(0.5))).astype(np.int32)
     else:
-        sym = lo.quantize(v)
+        sym = to_sym(v, mutate)
     out["sym"] = _tr(sym).reshape(B, -1)
     yh = (sym.astype(F32) + mu).astype(F32)
     if c["yadd"] and mutate != "yadd_dropped":
@@ -343,7 +358,7 @@ def prep_check64(c, d, outs):
     e2 = np.where((e1 == 0) & (_rnd(v) == 0), 0.0, U * (np.abs(v) + e1))
     r, excl = _decision(v * m if mode != 0 else v, (e1 + e2) * (m if mode != 0 else 1.0))
     sym_got = outs["sym"].reshape(B, 32, HW).transpose(0, 2, 1)
-    bad = (sym_got != r) & ~excl
+    bad = (sym_got != r) & ~excl & _dec_mask(v * m if mode != 0 else v)
     res.append(("sym", not bad.any(), int(bad.sum()), int(excl.sum())))
     symf = sym_got.astype(np.float64)
     yh = symf + mu64
@@ -367,10 +382,32 @@ def prep_check64(c, d, outs):
     return res
 
 
+_NORMAL_ONLY = [None]          # None: every element is judged (check64); a dict {output: mask to leave out}: check64_normal is running
+FLT_MIN, FLT_MAX = 2.0 ** -126, float(np.finfo(np.float32).max)
+
+
+def _dec_mask(v64):
+    """decision outputs under check64_normal: judged where the float64 operand is finite and inside the int32 range"""
+    if _NORMAL_ONLY[0] is None:
+        return True
+    with np.errstate(invalid="ignore"):
+        return np.isfinite(v64) & (np.abs(v64) < 2.0 ** 31)
+
+
 def _bounded(name, got, ref, bound):
-    diff = np.abs(np.asarray(got, np.float64) - ref)
-    bad = ~(diff <= bound)
-    with np.errstate(invalid="ignore", divide="ignore"):
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        diff = np.abs(np.asarray(got, np.float64) - ref)
+        if _NORMAL_ONLY[0] is not None:
+            ref, bound = np.broadcast_to(ref, diff.shape), np.broadcast_to(bound, diff.shape)
+            judged = np.isfinite(ref) & ((np.abs(ref) >= FLT_MIN) | (ref == 0)) & (np.abs(ref) <= FLT_MAX) & np.isfinite(bound)
+            out = _NORMAL_ONLY[0].get(name)
+            if out is not None:
+                judged &= ~np.broadcast_to(out, diff.shape)
+            bad = judged & ~(diff <= bound)
+            ratio = float(np.max(np.where(judged, np.where(np.isfinite(diff), diff / bound, np.inf), 0.0))) if judged.any() else 0.0
+            _NORMAL_ONLY.append((name, int(judged.sum()), int(judged.size)))
+            return (name, not bad.any(), ratio, 0)
+        bad = ~(diff <= bound)
         ratio = float(np.max(np.where(np.isfinite(diff), diff / bound, np.inf))) if diff.size else 0.0
     return (name, not bad.any(), ratio, 0)
 
@@ -758,7 +795,7 @@ def eb_restate(c, d, mutate=None):
     B, HW, Cc = c["B"], c["HW"], c["C"]
     med = d["med"]
     if c["kind"] == "EB_QUANT":
-        sym = lo.quantize((d["z"] - med).astype(F32))
+        sym = to_sym((d["z"] - med).astype(F32), mutate)
         return dict(sym=_tr(sym).reshape(B, -1), out=(sym.astype(F32) + med).astype(F32).reshape(B * HW, Cc))
     if c["kind"] == "EB_DEQUANT":
         s = d["sym"].transpose(0, 2, 1).astype(F32)
@@ -778,7 +815,7 @@ def eb_check64(c, d, outs):
         v = d["z"].astype(np.float64) - med
         r, excl = _decision(v, _rnd(v))
         got = outs["sym"].reshape(B, Cc, HW).transpose(0, 2, 1)
-        bad = (got != r) & ~excl
+        bad = (got != r) & ~excl & _dec_mask(v)
         zh = got.astype(np.float64) + med
         return [("sym", not bad.any(), int(bad.sum()), int(excl.sum())),
                 _bounded("out", outs["out"], zh.reshape(B * HW, Cc), 2 * _rnd(zh).reshape(B * HW, Cc) + TINY)]
@@ -1111,6 +1148,20 @@ def check64(c, d, outs):
     ok = all(r[1] for r in res) and all(r[3] <= cap for r in res)
     ratios = [r[2] for r in res if isinstance(r[2], float)]
     return ok, res, (max(ratios) if ratios else 0.0)
+
+
+def check64_normal(c, d, outs, exclude=None):
+    """check64 for operands outside the ordinary (tests/hostile_values.py): the same references and the same bounds, asserted on the
+    elements whose float64 value is finite and zero or of normal range and whose bound is finite -- less `exclude`, {output: mask}, where
+    float64 says nothing about the float32 contract (a square that overflows in float32 only); symbols are judged where the float64
+    operand is finite and inside the int32 range.  (ok, results, worst ratio, [(output, judged, of)])"""
+    _NORMAL_ONLY[:] = [dict(exclude or {})]
+    try:
+        with np.errstate(all="ignore"):
+            ok, res, ratio = check64(c, d, outs)
+        return ok, res, ratio, list(_NORMAL_ONLY[1:])
+    finally:
+        _NORMAL_ONLY[:] = [None]
 
 
 def specs(c, d):

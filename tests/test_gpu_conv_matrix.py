@@ -201,6 +201,25 @@ def check_out(c, d, o, val, what):
     assert not bad.any(), f"{c['name']} {what}: {int(bad.sum())} of {int((~exp_sent).sum())} outputs differ from the restatement"
 
 
+def check_out_nan(c, d, o, val, what):
+    """check_out for operands outside the ordinary (tests/test_gpu_hostile_values.py): every sentinel word holds, every output equals
+    the restatement bit for bit -- except that where both are NaN only NaN-ness is compared (the payload a NaN operation keeps is not
+    part of the contract).  Returns the count of such NaN pairs whose payloads differ."""
+    got = o.host()
+    want = o.expected(val)
+    exp_sent = want == SENT
+    bad_sent = exp_sent & (got != SENT)
+    assert not bad_sent.any(), f"{c['name']} {what}: {int(bad_sent.sum())} sentinel words overwritten " \
+                               f"(first at buffer word {int(np.argmax(bad_sent))}, guard {GUARD})"
+    both_nan = ~exp_sent & np.isnan(got.view(np.float32)) & np.isnan(want.view(np.float32))
+    bad = ~exp_sent & (((got != want) & ~both_nan) | (got == SENT))       # an output that still reads as the sentinel was never stored
+    if bad.any():
+        i = int(np.argmax(bad))
+        raise AssertionError(f"{c['name']} {what}: {int(bad.sum())} of {int((~exp_sent).sum())} outputs differ from the restatement, "
+                             f"first at buffer word {i}: got {got[i]:#010x}, restatement {want[i]:#010x}")
+    return int((both_nan & (got != want)).sum())
+
+
 def values(o):
     """the output tensor's values [B, outH, outW, C] read back from its buffer"""
     B, oh, ow, oc = o.shape
