@@ -1,7 +1,16 @@
-"""What the thirteen image-side modules (pixels, tiles, rate, frames, frame_tiles, frame_rate, clips, clip_rate, clip_tol, clip_tol_rate,
-chroma, chroma_tiles, metrics), the fourteenth, chroma_rate, and the fifteenth, chroma_clips, share in loading their libraries: the "library missing" ImportError, CDLL, a prototype table applied in one loop, and the base error class that
-formats a status code with the library's own strerror and its last HIP error.  Each module keeps its own LIB_PATH, EXPORTS, lib() and
-error class and defines them through this one; each library is still a file of its own that links no other.
+"""What the image-side modules share in loading their libraries: the "library missing" ImportError, CDLL, a prototype table applied
+in one loop, and the base error class that formats a status code with the library's own strerror and its last HIP error.  Each module
+keeps its own LIB_PATH, EXPORTS, lib() and error class and defines them through this one; each library is still a file of its own
+that links no other.  The thirteen modules that shared this when it was written:
+
+  pixels, tiles, rate, metrics
+  frames, frame_tiles, frame_rate
+  clips, clip_rate, clip_tol, clip_tol_rate
+  chroma, chroma_tiles
+
+and since then also:
+
+  chroma_rate, chroma_clips
 """
 import ctypes as C
 import os

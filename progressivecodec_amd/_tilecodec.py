@@ -1,9 +1,12 @@
-"""What the tile and clip layers share on the host: the frame-parameter bytes of PCF1 / PCG1 / PCS1 / PCS2, the
+"""What the tile and clip layers share on the host: the frame-parameter bytes of PCF1 / PCG1 / PCS1 / PCS2 and
+of PCH1 / PCK1 / PCL1, the
 tile table of PCT1 / PCT2 / PCS1 / PCS2 and the check of one of its entries, the encode loop, the decode loop and the argument
 checks with fixed texts.  No library of its own and no device call: what needs a device -- the cut of a chunk of tiles, the
 measurement of its decoded levels -- comes in as a callable, so everything here runs against a fake model on the host.
 
   frame_params      (fmt, matrix, range, upsample, bits) bytes -> names, or the container's refusal
+  sited_head        the ten bytes of PCH1 / PCK1 / PCL1 (format as layout, shift, sx, sy; siting; matrix, range, upsample, bits)
+  sited_params      those ten bytes -> names, or the container's refusal
   tile_table        header numbers -> (grid, [(offset, length)], payload start): geometry, "the whole table is there", the read
   entry_bytes       one table entry -> (the tile's PCB1 bytes, its parsed header), checked against buffer, tile size and contract
   encode_items      chunk, cut, compress_levels [, decompress_levels, measure], container.pack
@@ -30,6 +33,28 @@ def frame_params(f, m, r, u, bits, name):
     if bits != bits_of(fi[f]):
         raise ContainerError(f"corrupt {name} header: {bits} bits for {fi[f]!r}")
     return {"fmt": fi[f], "matrix": mi[m], "range": ri[r], "upsample": ui[u], "bits": bits}
+
+
+def sited_head(fmt, matrix, range, upsample, siting):
+    """the ten frame-parameter bytes of PCH1 / PCK1 / PCL1: layout, shift, sx, sy, horizontal siting, vertical siting, matrix, range,
+    upsample, bits"""
+    from .chroma import FORMATS, SITINGS, _MATRIX_ID
+    from .frames import RANGES, UPSAMPLES
+    f, (hs, vs) = FORMATS[fmt], SITINGS[siting]
+    return f.layout, f.shift, f.sx, f.sy, hs, vs, _MATRIX_ID[matrix], RANGES[range], UPSAMPLES[upsample], f.bits
+
+
+def sited_params(lay, sh, sx, sy, hs, vs, m, r, u, bits, name):
+    """sited_head's ten bytes, read from the container `name` -> dict(fmt, siting, matrix, range, upsample, bits)"""
+    from .chroma import FORMATS, SITINGS, _MATRIX_ID, _inv
+    from .frames import RANGES, UPSAMPLES
+    fi, si, mi, ri, ui = _inv(FORMATS), _inv(SITINGS), _inv(_MATRIX_ID), _inv(RANGES), _inv(UPSAMPLES)
+    if bits not in (8, 10):
+        raise ContainerError(f"corrupt {name} header: {bits} bits")
+    if (lay, bits, sh, sx, sy) not in fi or (hs, vs) not in si or m not in mi or r not in ri or u not in ui:
+        raise ContainerError(f"corrupt {name} header: layout {lay}, shift {sh} at {bits} bits, subsampling {sx}x{sy}, siting {hs}, {vs}, "
+                             f"matrix {m}, range {r}, upsample {u}")
+    return {"fmt": fi[(lay, bits, sh, sx, sy)], "siting": si[(hs, vs)], "matrix": mi[m], "range": ri[r], "upsample": ui[u], "bits": bits}
 
 
 def tile_table(buf, at, H, W, T, O, ny, nx, frames=1, head="header", what="image", table="tile table"):

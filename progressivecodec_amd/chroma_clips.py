@@ -43,7 +43,7 @@ import struct
 
 from . import _imagelib, _tilecodec, clips
 from ._lib import PC_OK
-from .chroma import FORMATS, SITINGS, _MATRIX_ID, _check_enums, _frame_view, _inv
+from .chroma import FORMATS, SITINGS, _MATRIX_ID, _check_enums, _frame_view, _inv  # noqa: F401
 from .chroma_tiles import _admissible_window, _one_frame, covering, pack_frame_tiled, stitch_frame
 from .clips import ClipPlan, source_table
 from .container import ContainerError
@@ -210,9 +210,8 @@ def pack_clip(blobs, source, H, W, tile, overlap, fmt, matrix, range, upsample, 
     g = grid_of(H, W, tile, overlap)
     F = clips._check_source(blobs, source, g)
     contract = container.build_contract_id() if contract is None else int(contract)
-    f, (hs, vs) = FORMATS[fmt], SITINGS[siting]
-    head = MAGIC + struct.pack(_HEAD, VERSION, f.layout, f.shift, f.sx, f.sy, hs, vs, _MATRIX_ID[matrix], RANGES[range], UPSAMPLES[upsample],
-                               f.bits, contract, g.H, g.W, g.T, g.O, g.ny, g.nx, F)
+    head = MAGIC + struct.pack(_HEAD, VERSION, *_tilecodec.sited_head(fmt, matrix, range, upsample, siting), contract, g.H, g.W, g.T, g.O,
+                               g.ny, g.nx, F)
     return head + clips._table_and_payload(len(head), blobs, source)
 
 
@@ -223,20 +222,14 @@ def _parse(buf, magic):
         raise ContainerError(f"not a {name} container")
     if len(buf) < HEADER_BYTES:
         raise ContainerError(f"truncated {name} header")
-    ver, lay, sh, sx, sy, hs, vs, m, r, u, bits, contract, H, W, T, O, ny, nx, F = struct.unpack_from(_HEAD, buf, 4)
+    ver, *sited, contract, H, W, T, O, ny, nx, F = struct.unpack_from(_HEAD, buf, 4)
     if ver != VERSION:
         raise ContainerError(f"unsupported {name} version {ver}")
-    fi, si, mi, ri, ui = _inv(FORMATS), _inv(SITINGS), _inv(_MATRIX_ID), _inv(RANGES), _inv(UPSAMPLES)
-    if bits not in (8, 10):
-        raise ContainerError(f"corrupt {name} header: {bits} bits")
-    if (lay, bits, sh, sx, sy) not in fi or (hs, vs) not in si or m not in mi or r not in ri or u not in ui:
-        raise ContainerError(f"corrupt {name} header: layout {lay}, shift {sh} at {bits} bits, subsampling {sx}x{sy}, siting {hs}, {vs}, "
-                             f"matrix {m}, range {r}, upsample {u}")
+    params = _tilecodec.sited_params(*sited, name)
     g, pairs, start = _tilecodec.tile_table(buf, HEADER_BYTES, H, W, T, O, ny, nx, F, f"{name} header", "frame", f"{name} table")
     clips._equal_or_disjoint(pairs, name)
     n = ny * nx
-    return {"fmt": fi[(lay, bits, sh, sx, sy)], "siting": si[(hs, vs)], "matrix": mi[m], "range": ri[r], "upsample": ui[u], "bits": bits,
-            "contract": contract, "grid": g, "F": F, "table": [pairs[k * n:(k + 1) * n] for k in _range(F)], "payload_start": start}
+    return dict(params, contract=contract, grid=g, F=F, table=[pairs[k * n:(k + 1) * n] for k in _range(F)], payload_start=start)
 
 
 def parse_clip(buf):

@@ -28,23 +28,25 @@ PSNR, measuring in an output format other than the stored one, batches of frames
 import collections
 import ctypes as C
 
-from . import _imagelib, _tilecodec
-from ._lib import PC_OK
+from . import _imagelib, _yuvlayers
+from . import chroma_tiles  # noqa: F401  (the layer below: its cut and its container)
 from ._tilecodec import max_tile  # noqa: F401
-from .chroma import FORMATS, SITINGS, _check_enums
-from .chroma_tiles import HEADER_BYTES as FRAME_HEADER_BYTES
-from .chroma_tiles import ChromaTilesError, _one_frame, pack_frame_tiled
-from .frames import RANGES, UPSAMPLES, Frame, _frame_struct, coefficients
-from .rate import TABLE_ENTRY_BYTES, allocate
-from .tiles import HEADER_BYTES, TileGrid, _check_tiles, _fit_tiles, grid_of, pack_tiled
+from .chroma import FAMILY, FORMATS, SITINGS
+from .frames import Frame
+from .tiles import TileGrid
+# the names the layers above and the tests reach through this module
+from .chroma import _check_enums  # noqa: F401
+from .chroma_tiles import HEADER_BYTES as FRAME_HEADER_BYTES  # noqa: F401
+from .chroma_tiles import ChromaTilesError, _one_frame, pack_frame_tiled  # noqa: F401
+from .frames import RANGES, UPSAMPLES, _frame_struct, coefficients  # noqa: F401
+from .rate import TABLE_ENTRY_BYTES, allocate  # noqa: F401
+from .tiles import HEADER_BYTES, _check_tiles, _fit_tiles, grid_of, pack_tiled  # noqa: F401
 
 LIB_PATH = _imagelib.lib_path("chroma_rate")
 
 #: every symbol chroma_rate_hip/pc_chroma_rate.h declares
 EXPORTS = ["pc_chroma_rate_workspace_size", "pc_chroma_rate_tile_sse", "pc_chroma_rate_plan", "pc_chroma_rate_strerror",
            "pc_chroma_rate_last_hip_error"]
-
-_range = range                            # the functions below take a parameter of that name
 
 
 def _prototypes():
@@ -87,57 +89,14 @@ def frame_tile_distortion(x_hat_tiles, grid, ref, fmt, matrix="bt709", range="li
     whole original H x W frame in `fmt` (chroma.py's tuple of planes, any row strides) whose chroma is sited as `siting` says -> int64
     cuda [n,3]: per tile and plane [Y, Cb, Cr] the sum over the tile's samples inside the frame of weight * (code - refcode)^2, exact
     (pc_chroma_rate.h).  A tile's sums do not depend on which range it is part of."""
-    import torch
-    _check_enums(fmt, matrix, range, siting=siting)
-    g = TileGrid(*grid)
-    full = grid_of(g.H, g.W, g.T, g.O)
-    if (full.ny, full.nx) != (g.ny, g.nx):
-        raise ValueError(f"{g}: the grid of a {g.H}x{g.W} frame is {full.ny}x{full.nx}")
-    _tilecodec.tile_limit(g.T, fmt)
-    x = x_hat_tiles
-    n = int(x.shape[0]) if torch.is_tensor(x) and x.dim() == 4 else 0
-    first_tile = int(first_tile)
-    if n < 1 or first_tile < 0 or first_tile + n > full.ny * full.nx:
-        raise ValueError(f"tiles {first_tile} .. {first_tile + n - 1} lie outside the {full.ny}x{full.nx} grid"
-                         if n else "x_hat_tiles must be a [n,3,T,T] tensor with n >= 1")
-    _check_tiles(x, full._replace(nty=1, ntx=n))
-    rts, rH, rW = _one_frame(ref, fmt, "ref")
-    if (rH, rW) != (g.H, g.W) or rts[0].device != x.device:
-        raise ValueError(f"ref must be the {g.H}x{g.W} frame on {x.device}, got {rH}x{rW} on {rts[0].device}")
-    if x.device.type != "cuda":
-        raise ValueError(f"x_hat_tiles must be on a GPU (there is no CPU fallback), got {x.device}")
-    x = _fit_tiles(x, g.T)
-    k = coefficients(matrix)
-    f, (hs, vs) = FORMATS[fmt], SITINGS[siting]
-    L = lib()
-    rst = _frame_struct(rts)
-    with torch.cuda.device(x.device):
-        nbytes = L.pc_chroma_rate_workspace_size(g.T, f.sy, n)
-        ws = torch.empty(nbytes // 8, dtype=torch.int64, device=x.device)
-        out = torch.empty((n, 3), dtype=torch.int64, device=x.device)
-        rc = L.pc_chroma_rate_tile_sse(x.data_ptr(), x.stride(0), x.stride(1), x.stride(2), g.H, g.W, g.T, g.O, first_tile, n, *f, hs, vs,
-                                       RANGES[range], k.kr, k.kg, k.kb, k.ib, k.ir, C.byref(rst), ws.data_ptr(), nbytes, out.data_ptr(),
-                                       torch.cuda.current_stream(x.device).cuda_stream)
-    del rts
-    if rc != PC_OK:
-        raise ChromaRateError(rc, "pc_chroma_rate_tile_sse")
-    return out
+    return _yuvlayers.frame_tile_distortion(FAMILY, x_hat_tiles, grid, ref, fmt, matrix, range, siting, first_tile)
 
 
 def plan(x_hat_tiles, ref, fmt, overlap=0):
     """pc_chroma_rate_plan for tensors (host only, nothing is launched or copied): True where frame_tile_distortion of exactly these
     tensors with this overlap takes the wide-access path.  ref is a tuple of batched tensors ([1,...]) whose strides already fit a
     frame."""
-    _check_enums(fmt)
-    f = FORMATS[fmt]
-    x = x_hat_tiles
-    wide = C.c_int(-1)
-    rf = _frame_struct(ref)
-    rc = lib().pc_chroma_rate_plan(x.data_ptr(), x.stride(0), x.stride(1), x.stride(2), int(overlap), f.layout, f.bits, f.sx, C.byref(rf),
-                                   C.byref(wide))
-    if rc != PC_OK:
-        raise ChromaRateError(rc, "pc_chroma_rate_plan")
-    return bool(wide.value)
+    return _yuvlayers.rate_plan(FAMILY, x_hat_tiles, ref, fmt, overlap)
 
 
 def encode_frame_tiled_to_size(model, planes, qualities, target_bytes, fmt, matrix="bt709", range="limited", upsample="linear",
@@ -151,46 +110,6 @@ def encode_frame_tiled_to_size(model, planes, qualities, target_bytes, fmt, matr
     tiles are cut, coded at every level (compress_levels), decoded again (decompress_levels) and measured max_tiles_per_call at a
     time, so a call holds at most max_tiles_per_call * (1 + len(qualities)) tile tensors on the device; neither the bytes nor the
     plan depend on it.  The container holds a PCT2 container (one level per tile); chroma_tiles.decode_frame_tiled reads it."""
-    import torch
-    from . import chroma_tiles
-    qualities = _tilecodec.levels_of(qualities)
-    _check_enums(fmt, matrix, range, upsample, siting)
-    step = _tilecodec.tiles_per_call(max_tiles_per_call)
-    pw = _tilecodec.plane_weights_of(plane_weights)
-    target_bytes = int(target_bytes)
-    ts, H, W = _one_frame(planes, fmt, "planes")
-    g = grid_of(H, W, tile, overlap)
-    _tilecodec.tile_limit(g.T, fmt)
-    n = g.ny * g.nx
-    importance = _tilecodec.importance_of(importance, g)
-    k = coefficients(matrix)
-    f, (hs, vs) = FORMATS[fmt], SITINGS[siting]
-    dev = ts[0].device
-    src = _frame_struct(ts)
-    CL = chroma_tiles.lib()
-
-    def cut(a, b):
-        with torch.cuda.device(dev):
-            x = torch.empty((b, 3, g.T, g.T), dtype=torch.float32, device=dev)
-            m0 = 0
-            for i, j, m in _tilecodec.row_pieces(a, b, g.nx):
-                rc = CL.pc_chroma_tiles_cut(C.byref(src), *f, hs, vs, RANGES[range], UPSAMPLES[upsample], k.a, k.b, k.c, k.d, H, W, g.T, g.O,
-                                            i, j, 1, m, x[m0:].data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
-                if rc != PC_OK:
-                    raise ChromaTilesError(rc, "pc_chroma_tiles_cut")
-                m0 += m
-        return x
-
-    def measure(a, b, decoded):
-        d = torch.stack([frame_tile_distortion(o["x_hat"], g, ts, fmt, matrix, range, siting, a) for o in decoded], 1).tolist()
-        return [[[int(v) for v in row] for row in per_level] for per_level in d]                                # [b][levels][3]
-    bufs, plane_dists = _tilecodec.encode_items(model, n, step, qualities, mask_pol, g.T, cut, measure)
-    del ts
-    rates = [[TABLE_ENTRY_BYTES + len(p) for p in row] for row in bufs]
-    dists = [[pw[0] * v[0] + pw[1] * v[1] + pw[2] * v[2] for v in row] for row in plane_dists]
-    levels = allocate(rates, dists, target_bytes - FRAME_HEADER_BYTES - HEADER_BYTES, importance)
-    inner = pack_tiled([bufs[t][levels[t]] for t in _range(n)], g.H, g.W, g.T, g.O, per_tile_levels=True)
-    buf = pack_frame_tiled(inner, fmt, matrix, range, upsample, siting)
-    sse = [sum(plane_dists[t][levels[t]][p] for t in _range(n)) for p in _range(3)]
-    return buf, ChromaRatePlan(levels, rates, dists, plane_dists, 2 * g.O if g.O else 1, len(buf),
-                               sum(dists[t][levels[t]] for t in _range(n)), sse, sse_exact(g, fmt, siting))
+    buf, fields, g = _yuvlayers.encode_frame_tiled_to_size(FAMILY, model, planes, qualities, target_bytes, fmt, matrix, range, upsample, siting, tile,
+                                                           overlap, mask_pol, plane_weights, importance, max_tiles_per_call)
+    return buf, ChromaRatePlan(*fields, sse_exact(g, fmt, siting))

@@ -28,11 +28,11 @@ chroma_tiles.py's.  Out of scope: compress_with_ac.
 import ctypes as C
 import struct
 
-from . import _imagelib, _tilecodec
-from ._lib import PC_OK
-from .frames import (FORMATS, RANGES, UPSAMPLES, _MATRIX_ID, Distortion, Frame, _check_enums, _frame_struct, _frame_view, bits_of, coefficients,
-                     empty_frame)
-from .tiles import TileGrid, _check_tiles, _fit_tiles, _window, grid_of
+from . import _imagelib, _yuvlayers
+from .frames import FAMILY, Frame
+# the names the layers above and the tests reach through this module
+from .frames import FORMATS, RANGES, UPSAMPLES, _MATRIX_ID, Distortion, _check_enums, _frame_struct, _frame_view, bits_of, coefficients, empty_frame  # noqa: F401
+from .tiles import TileGrid, _check_tiles, _fit_tiles, _window, grid_of  # noqa: F401
 
 LIB_PATH = _imagelib.lib_path("frame_tiles")
 
@@ -68,68 +68,32 @@ class FrameTilesError(_imagelib.ImageLibError):
 
 def admissible(window, H, W):
     """whether (y0, x0, h, w), a window inside an H x W frame, has the frame's own chroma samples (the module's docstring)"""
-    y0, x0, h, w = window
-    return y0 % 2 == 0 and x0 % 2 == 0 and (h % 2 == 0 or y0 + h == H) and (w % 2 == 0 or x0 + w == W)
+    return _yuvlayers.admissible(FAMILY, window, H, W, "nv12")       # the three formats have the same 2 x 2 cells
 
 
 def _admissible_window(window, H, W):
-    y0, x0, h, w = _window((0, 0, H, W) if window is None else window, H, W)
-    if not admissible((y0, x0, h, w), H, W):
-        raise ValueError(f"window {(y0, x0, h, w)} of the {H}x{W} frame is not admissible: y0 and x0 must be even, h even or y0 + h == H, "
-                         "w even or x0 + w == W")
-    return y0, x0, h, w
+    return _yuvlayers.admissible_window(FAMILY, window, H, W, "nv12")
 
 
 def _one_frame(planes, fmt, what):
     """frames._frame_view for ONE frame: (tensors kept alive, H, W)"""
-    import torch
-    if isinstance(planes, (tuple, list)) and planes and torch.is_tensor(planes[0]) and planes[0].dim() == 3 and planes[0].shape[0] != 1:
-        raise ValueError(f"{what} must be one frame, got a batch of {planes[0].shape[0]}")
-    ts, _, H, W, _ = _frame_view(planes, fmt, what)
-    return ts, H, W
+    return _yuvlayers.one_frame(FAMILY, planes, fmt, what)
 
 
 def cut_frame(planes, fmt, matrix="bt709", range="limited", upsample="linear", tile=512, overlap=0, rect=None):
     """frame -> (tiles, grid): float32 [n,3,T,T], the tiles of `rect` = (ty0, tx0, nty, ntx) (default: the whole grid) row-major, each
     the crop over [i*S, i*S + T) per axis of what frames.to_model_input computes for the whole frame (the chroma taps clamp at the
     frame's edges, never at a tile's) and +0.0 beyond the frame, and the TileGrid that says so."""
-    import torch
-    _check_enums(fmt, matrix, range, upsample)
-    ts, H, W = _one_frame(planes, fmt, "planes")
-    g = grid_of(H, W, tile, overlap)
-    if rect is not None:
-        g = g.with_rect(rect)
-    k = coefficients(matrix)
-    dev = ts[0].device
-    src = _frame_struct(ts)
-    with torch.cuda.device(dev):
-        out = torch.empty((g.n, 3, g.T, g.T), dtype=torch.float32, device=dev)
-        rc = lib().pc_frame_tiles_cut(C.byref(src), FORMATS[fmt], RANGES[range], UPSAMPLES[upsample], k.a, k.b, k.c, k.d, H, W, g.T, g.O,
-                                      *g.rect, out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
-    if rc != PC_OK:
-        raise FrameTilesError(rc, "pc_frame_tiles_cut")
-    return out, g
+    return _yuvlayers.cut_frame(FAMILY, planes, fmt, matrix, range, upsample, None, tile, overlap, rect)
 
 
 def _offset_frame(ts, fmt, y0, x0):
     """the Frame of the window whose first luma sample is (y0, x0) (both even) of the frame held by the batched tensors ts"""
-    f = _frame_struct(ts)
-    es = ts[0].element_size()
-    f.y = ts[0].data_ptr() + es * (y0 * ts[0].stride(1) + x0)
-    if fmt == "i420":
-        f.u = ts[1].data_ptr() + es * ((y0 // 2) * ts[1].stride(1) + x0 // 2)
-        f.v = ts[2].data_ptr() + es * ((y0 // 2) * ts[2].stride(1) + x0 // 2)
-    else:
-        f.u = ts[1].data_ptr() + es * ((y0 // 2) * ts[1].stride(1) + x0)
-    return f
+    return _yuvlayers.offset_frame(FAMILY, ts, fmt, y0, x0)
 
 
 def _full_grid(grid):
-    g = TileGrid(*grid)
-    full = grid_of(g.H, g.W, g.T, g.O)
-    if (full.ny, full.nx) != (g.ny, g.nx):
-        raise ValueError(f"{g}: the grid of a {g.H}x{g.W} frame is {full.ny}x{full.nx}")
-    return full.with_rect(g.rect)
+    return _yuvlayers.full_grid(grid)
 
 
 def stitch_frame(x_hat_tiles, grid, fmt, matrix="bt709", range="limited", window=None, ref=None, image=True):
@@ -138,49 +102,7 @@ def stitch_frame(x_hat_tiles, grid, fmt, matrix="bt709", range="limited", window
     batch axis: every covering tile clamped to [0, 1] and blended with the band weights (tiles.stitch's m), then frames' emit on m.
     The rectangle must hold every tile that covers a window pixel.  With ref (the whole original H x W frame in `fmt`) returns
     (frame, Distortion) with the sums over the window; with image=False (needs ref) the Distortion alone."""
-    import torch
-    if not image and ref is None:
-        raise ValueError("image=False leaves nothing to compute without ref")
-    _check_enums(fmt, matrix, range)
-    g = _full_grid(grid)
-    _check_tiles(x_hat_tiles, g)
-    y0, x0, h, w = _admissible_window(window, g.H, g.W)
-    need = g.covering((y0, x0, h, w))
-    if need[0] < g.ty0 or need[1] < g.tx0 or need[0] + need[2] > g.ty0 + g.nty or need[1] + need[3] > g.tx0 + g.ntx:
-        raise ValueError(f"window {(y0, x0, h, w)} needs the tiles {need}, x_hat_tiles holds {g.rect}")
-    x = x_hat_tiles
-    rts = None
-    if ref is not None:
-        rts, rH, rW = _one_frame(ref, fmt, "ref")
-        if (rH, rW) != (g.H, g.W) or rts[0].device != x.device:
-            raise ValueError(f"ref must be the {g.H}x{g.W} frame on {x.device}, got {rH}x{rW} on {rts[0].device}")
-    if x.device.type != "cuda":
-        raise ValueError(f"x_hat_tiles must be on a GPU (there is no CPU fallback), got {x.device}")
-    x = _fit_tiles(x, g.T)
-    k = coefficients(matrix)
-    L = lib()
-    with torch.cuda.device(x.device):
-        out = empty_frame(fmt, 1, h, w, x.device) if image else None
-        dst = _frame_struct(out) if image else None
-        rst = _offset_frame(rts, fmt, y0, x0) if rts is not None else None
-        ws = sse = None
-        nbytes = 0
-        if rts is not None:
-            nbytes = L.pc_frame_tiles_stitch_workspace_size(x0, h, w)
-            ws = torch.empty(nbytes // 8, dtype=torch.int64, device=x.device)
-            sse = torch.empty((1, 3), dtype=torch.int64, device=x.device)
-        rc = L.pc_frame_tiles_stitch(x.data_ptr(), x.stride(0), x.stride(1), x.stride(2), g.H, g.W, g.T, g.O, *g.rect, y0, x0, h, w,
-                                     FORMATS[fmt], RANGES[range], k.kr, k.kg, k.kb, k.ib, k.ir, C.byref(dst) if dst is not None else None,
-                                     C.byref(rst) if rst is not None else None, ws.data_ptr() if ws is not None else None, nbytes,
-                                     sse.data_ptr() if sse is not None else None, torch.cuda.current_stream(x.device).cuda_stream)
-    del rts
-    if rc != PC_OK:
-        raise FrameTilesError(rc, "pc_frame_tiles_stitch")
-    dist = Distortion(sse, h, w, bits_of(fmt)) if sse is not None else None
-    if not image:
-        return dist
-    out = tuple(t[0] for t in out)
-    return (out, dist) if dist is not None else out
+    return _yuvlayers.stitch_frame(FAMILY, x_hat_tiles, grid, fmt, matrix, range, None, window, ref, image)
 
 
 def plan(op, planes, fmt, f32, overlap=0, x0=0, ref=None):
@@ -188,15 +110,7 @@ def plan(op, planes, fmt, f32, overlap=0, x0=0, ref=None):
     frame, f32 the tile tensor, overlap the grid's) or the stitch (op = STITCH: planes the destination window or None, f32 the decoded
     tiles, x0 the window's first column, ref the original's window) of exactly these tensors takes the wide-access path.  planes and
     ref are tuples of batched tensors ([1,...]) whose strides already fit a frame."""
-    _check_enums(fmt)
-    wide = C.c_int(-1)
-    fr = _frame_struct(planes) if planes is not None else None
-    rf = _frame_struct(ref) if ref is not None else None
-    rc = lib().pc_frame_tiles_plan(op, FORMATS[fmt], C.byref(fr) if fr is not None else None, f32.data_ptr(), f32.stride(0), f32.stride(1),
-                                   f32.stride(2), int(overlap), int(x0), C.byref(rf) if rf is not None else None, C.byref(wide))
-    if rc != PC_OK:
-        raise FrameTilesError(rc, "pc_frame_tiles_plan")
-    return bool(wide.value)
+    return _yuvlayers.tiled_plan(FAMILY, op, planes, fmt, f32, overlap, x0, ref)
 
 
 # -- PCG1: a frame's parameters in front of one PCT1 / PCT2 container -----------------------------------------------------------------
@@ -204,34 +118,13 @@ def plan(op, planes, fmt, f32, overlap=0, x0=0, ref=None):
 def pack_frame_tiled(inner, fmt, matrix, range, upsample):
     """PCG1: the magic, the version byte, fmt, matrix, range, upsample and bits as one byte each, then the PCT1 / PCT2 container
     unmodified (its H, W are the frame's)."""
-    from . import container, tiles
-    _check_enums(fmt, matrix, range, upsample)
-    try:
-        tiles.parse_tiled(inner)
-    except container.ContainerError as e:
-        raise container.ContainerError(f"PCG1: the inner container does not parse: {e}") from None
-    return MAGIC + struct.pack(_HEAD, VERSION, FORMATS[fmt], _MATRIX_ID[matrix], RANGES[range], UPSAMPLES[upsample], bits_of(fmt)) + bytes(inner)
+    return _yuvlayers.pack_frame_tiled(FAMILY, inner, fmt, matrix, range, upsample, None)
 
 
 def parse_frame_tiled(buf):
     """-> dict(fmt, matrix, range, upsample, bits, H, W, inner (the PCT1 / PCT2 container), tiled (tiles.parse_tiled of it)).
     ContainerError on a bad magic, version, enum, bit depth, length or inner header; nothing else is touched."""
-    from . import container, tiles
-    if len(buf) < 4 or bytes(buf[:4]) != MAGIC:
-        raise container.ContainerError("not a PCG1 container")
-    if len(buf) < HEADER_BYTES:
-        raise container.ContainerError("truncated PCG1 header")
-    ver, f, m, r, u, bits = struct.unpack_from(_HEAD, buf, 4)
-    if ver != VERSION:
-        raise container.ContainerError(f"unsupported PCG1 version {ver}")
-    params = _tilecodec.frame_params(f, m, r, u, bits, "PCG1")
-    inner = bytes(buf[HEADER_BYTES:])
-    try:
-        hd = tiles.parse_tiled(inner)
-    except container.ContainerError as e:
-        raise container.ContainerError(f"PCG1: the inner container does not parse: {e}") from None
-    g = hd["grid"]
-    return dict(params, H=g.H, W=g.W, inner=inner, tiled=hd)
+    return _yuvlayers.parse_frame_tiled(FAMILY, buf)
 
 
 def encode_frame_tiled(model, planes, qualities, fmt, matrix="bt709", range="limited", upsample="linear", tile=512, overlap=0,
@@ -239,12 +132,8 @@ def encode_frame_tiled(model, planes, qualities, fmt, matrix="bt709", range="lim
     """frame -> one PCG1 container (bytes) holding every level of `qualities` for every tile.  The tiles are coded max_tiles_per_call
     at a time as one batch each (model.compress_levels), which bounds the device memory a call needs whatever the frame's size; the
     bytes do not depend on it.  The PCT1 container inside is what tiles.pack_tiled makes of the tiles' PCB1 containers."""
-    from . import tiles
-    qualities = [float(q) for q in qualities]
-    step = _tilecodec.tiles_per_call(max_tiles_per_call)
-    x, g = cut_frame(planes, fmt, matrix, range, upsample, tile, overlap)        # the whole frame in one launch
-    bufs = _tilecodec.encode_items(model, g.n, step, qualities, mask_pol, g.T, lambda a, b: x[a:a + b])
-    return pack_frame_tiled(tiles.pack_tiled(bufs, g.H, g.W, g.T, g.O), fmt, matrix, range, upsample)
+    return _yuvlayers.encode_frame_tiled(FAMILY, model, planes, qualities, fmt, matrix, range, upsample, None, tile, overlap, mask_pol,
+                                         max_tiles_per_call)
 
 
 def decode_frame_tiled(model, buf, level=-1, region=None, fmt=None, max_tiles_per_call=32):
@@ -252,14 +141,4 @@ def decode_frame_tiled(model, buf, level=-1, region=None, fmt=None, max_tiles_pe
     region = (y0, x0, h, w), in the stored format or in `fmt` when given (the stored matrix and range either way; another bit depth
     is computed from the decoder's float output, not converted from codes).  Only the tiles that cover the region are read and
     decoded (max_tiles_per_call at a time, one batch each); every refusal is a ContainerError raised before the model is touched."""
-    from . import container, tiles
-    step = _tilecodec.tiles_per_call(max_tiles_per_call)
-    hd = parse_frame_tiled(buf)
-    out_fmt = hd["fmt"] if fmt is None else fmt
-    _check_enums(out_fmt)
-    try:
-        window = _admissible_window(region, hd["H"], hd["W"])
-    except ValueError as e:
-        raise container.ContainerError(str(e)) from None
-    x_hat, g, window = tiles._decode_region_tiles(model, hd["inner"], level, window, step)
-    return stitch_frame(x_hat, g, out_fmt, hd["matrix"], hd["range"], window=window)
+    return _yuvlayers.decode_frame_tiled(FAMILY, model, buf, level, region, fmt, None, max_tiles_per_call)

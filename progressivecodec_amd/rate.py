@@ -25,7 +25,7 @@ from fractions import Fraction
 from . import _imagelib, _tilecodec
 from ._lib import PC_OK
 from .pixels import ROUNDINGS
-from .tiles import HEADER_BYTES, TileGrid, _check_tiles, _fit_tiles, _view3, grid_of, pack_tiled
+from .tiles import HEADER_BYTES, TileGrid, _check_tiles, _fit_tiles, _linear_tiles, _view3, grid_of, pack_tiled  # noqa: F401
 
 LIB_PATH = _imagelib.lib_path("rate")
 
@@ -60,6 +60,11 @@ class RateError(_imagelib.ImageLibError):
 RatePlan = collections.namedtuple("RatePlan", "levels rates dists den container_bytes predicted")
 
 
+def _tile_limit(T):
+    if T > 2048:
+        raise ValueError(f"tile must be at most 2048 for the distortion sums to fit 63 bits, got {T}")
+
+
 def tile_distortion(x_hat_tiles, grid, ref, first_tile=0, ref_layout="hwc", rounding="nearest"):
     """x_hat_tiles: float32 cuda [n,3,T,T], the decoded tiles first_tile .. first_tile + n - 1 of grid's row-major ny x nx grid (a
     linear range, not a rectangle; grid's own rectangle is ignored; any tile / channel / row strides, unit stride along a row), ref: the
@@ -68,19 +73,8 @@ def tile_distortion(x_hat_tiles, grid, ref, first_tile=0, ref_layout="hwc", roun
     import torch
     if rounding not in ROUNDINGS:
         raise ValueError(f"rounding must be 'nearest' or 'trunc', got {rounding!r}")
-    g = TileGrid(*grid)
-    full = grid_of(g.H, g.W, g.T, g.O)
-    if (full.ny, full.nx) != (g.ny, g.nx):
-        raise ValueError(f"{g}: the grid of a {g.H}x{g.W} image is {full.ny}x{full.nx}")
-    if g.T > 2048:
-        raise ValueError(f"tile must be at most 2048 for the distortion sums to fit 63 bits, got {g.T}")
-    x = x_hat_tiles
-    n = int(x.shape[0]) if torch.is_tensor(x) and x.dim() == 4 else 0
+    g, n, x = _linear_tiles(grid, x_hat_tiles, first_tile, "image", _tile_limit)
     first_tile = int(first_tile)
-    if n < 1 or first_tile < 0 or first_tile + n > full.ny * full.nx:
-        raise ValueError(f"tiles {first_tile} .. {first_tile + n - 1} lie outside the {full.ny}x{full.nx} grid"
-                         if n else "x_hat_tiles must be a [n,3,T,T] tensor with n >= 1")
-    _check_tiles(x, full._replace(nty=1, ntx=n))
     r4, rview, rhw = _view3(ref, ref_layout, "ref")
     if rhw != (g.H, g.W) or r4.device != x.device:
         raise ValueError(f"ref must be the {g.H}x{g.W} image on {x.device}, got {tuple(ref.shape)} on {ref.device}")
@@ -88,7 +82,6 @@ def tile_distortion(x_hat_tiles, grid, ref, first_tile=0, ref_layout="hwc", roun
         rview = rview[:3] + (max(rview[3], g.W * (3 if ref_layout == "hwc" else 1)),)
     if x.device.type != "cuda":
         raise ValueError(f"x_hat_tiles must be on a GPU (there is no CPU fallback), got {x.device}")
-    x = _fit_tiles(x, g.T)
     L = lib()
     with torch.cuda.device(x.device):
         nbytes = L.pc_rate_workspace_size(g.T, n)

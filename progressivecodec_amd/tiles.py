@@ -188,6 +188,26 @@ def _fit_tiles(x, T):
     return x if x.stride(3) == 1 and x.stride(2) >= T and min(x.stride()[:2]) >= 1 else x.contiguous()
 
 
+def _linear_tiles(grid, x_hat_tiles, first_tile, what, limit, *of):
+    """What the three tile distortions check first: grid is the grid of its `what` ("image", "frame"), limit(T, *of) passes,
+    x_hat_tiles is float32 [n,3,T,T] and the tiles first_tile .. first_tile + n - 1 lie in the grid -> (the whole grid, n, the tile
+    tensor as the kernels can take it)."""
+    import torch
+    g = TileGrid(*grid)
+    full = grid_of(g.H, g.W, g.T, g.O)
+    if (full.ny, full.nx) != (g.ny, g.nx):
+        raise ValueError(f"{g}: the grid of a {g.H}x{g.W} {what} is {full.ny}x{full.nx}")
+    limit(g.T, *of)
+    x = x_hat_tiles
+    n = int(x.shape[0]) if torch.is_tensor(x) and x.dim() == 4 else 0
+    first_tile = int(first_tile)
+    if n < 1 or first_tile < 0 or first_tile + n > full.ny * full.nx:
+        raise ValueError(f"tiles {first_tile} .. {first_tile + n - 1} lie outside the {full.ny}x{full.nx} grid"
+                         if n else "x_hat_tiles must be a [n,3,T,T] tensor with n >= 1")
+    _check_tiles(x, full._replace(nty=1, ntx=n))
+    return full, n, _fit_tiles(x, g.T)
+
+
 def stitch(x_hat_tiles, grid, window=None, layout="hwc", rounding="nearest", ref=None, ref_layout=None, image=True):
     """x_hat_tiles: float32 cuda [n,3,T,T], the decoded tiles of grid's rectangle (any tile / channel / row strides, unit stride along a
     row) -> uint8 [h,w,3] ("hwc") or [3,h,w] ("chw"): the window (y0, x0, h, w) of the image (default: all of it), every covering tile
