@@ -2,7 +2,7 @@
 // of pc_chroma.h's twelve formats and three chroma sitings, in the frame's own codes, on gfx950 (pc_chroma_rate.h).  Definition:
 // DESIGN.md section 24, the composition of sections 21 (the emit), 11 (geometry) and 12 (integer band weights).  Loads, levels and
 // the per-pixel colour arithmetic are image_csrc/pc_yuv_device.h's, the geometry and the band numerators image_csrc/pc_tile_grid.h's,
-// the reduction image_csrc/pc_reduce.h's.
+// the reduction image_csrc/pc_reduce.h's, the code of an element and the format checks image_csrc/pc_chroma_items.h's.
 //
 // A work item is SY rows of one tile (a row pair at 4:2:0, one row at 4:2:2 and 4:4:4) by eight tile-aligned columns, with the
 // 8 / SX chroma samples of those columns.  A thread takes one item, a block NT consecutive items of ONE tile (T * T / (8 SY) is a
@@ -25,12 +25,14 @@
 #include "pc_reduce.h"
 #include "pc_tile_grid.h"
 #include "pc_yuv_device.h"
-
-#include <type_traits>
+#include "pc_chroma_items.h"
 
 #include "pc_chroma_rate.h"
 
 namespace {
+
+static_assert(PC_CHR_PLANAR == LAYOUT_PLANAR && PC_CHR_SEMIPLANAR == LAYOUT_SEMIPLANAR, "pc_chroma_items.h's layouts are pc_chroma_rate.h's");
+static_assert(PC_CHR_CENTRE == SITE_CENTRE && PC_CHR_COSITED == SITE_COSITED, "pc_chroma_items.h's sitings are pc_chroma_rate.h's");
 
 constexpr int T_MAX8 = 2048;             // T^4 * 255^2 < 2^60
 constexpr int T_MAX10 = 1024;            // T^4 * 1023^2 < 2^60
@@ -46,11 +48,6 @@ struct Measure {
     float s;
     int sh;
 };
-
-// The code of an element.  An 8-bit element is its code, which the 8-bit instantiations know at compile time; a 16-bit word carries
-// a wave-uniform shift and may hold other bits.
-template <class T>
-__device__ __forceinline__ unsigned code_in(unsigned w, int sh, unsigned mask) { return sizeof(T) == 1 ? w : (w >> sh) & mask; }
 
 // One row of an item: the floats of tile columns q0 .. q0+7 at xr (channel stride sc; xr is column 0 of the tile's row), of which
 // the lanes 0 .. hi-1 lie inside the frame -> the row's horizontally filtered chroma differences h[Cb, Cr][8 / SX] and, where the
@@ -113,7 +110,7 @@ __device__ __forceinline__ void weighted_row(const float* xr, int64_t sc, int q0
 #pragma unroll
     for (int q = 0; q < COLS; ++q) {
         if (FULL || q < hi) {
-            const int e = (int)yq[q] - (int)code_in<T>(w[q], ms.sh, (unsigned)lv.maxv);
+            const int e = (int)yq[q] - (int)code_of<T>(w[q], ms.sh, (unsigned)lv.maxv);
             row += (u64)(ax[q] * (unsigned)(e * e));
         }
     }
@@ -189,8 +186,8 @@ __device__ __forceinline__ void sse_item(const float* xt, int64_t sc, int64_t sh
 #pragma unroll
     for (int j = 0; j < NC; ++j) {
         if (FULL || j < nc) {
-            const int eb = clampi((int)rintf(v[0][j] * ms.s + (float)lv.co), 0, lv.maxv) - (int)code_in<T>(w[0][j], ms.sh, (unsigned)lv.maxv);
-            const int er = clampi((int)rintf(v[1][j] * ms.s + (float)lv.co), 0, lv.maxv) - (int)code_in<T>(w[1][j], ms.sh, (unsigned)lv.maxv);
+            const int eb = clampi((int)rintf(v[0][j] * ms.s + (float)lv.co), 0, lv.maxv) - (int)code_of<T>(w[0][j], ms.sh, (unsigned)lv.maxv);
+            const int er = clampi((int)rintf(v[1][j] * ms.s + (float)lv.co), 0, lv.maxv) - (int)code_of<T>(w[1][j], ms.sh, (unsigned)lv.maxv);
             const unsigned cx = SX == 2 ? (ax[SX * j] + ax[SX * j + SX - 1]) >> 1 : ax[j];
             sb += (u64)(cx * (unsigned)(eb * eb));
             sr += (u64)(cx * (unsigned)(er * er));
@@ -239,36 +236,6 @@ __global__ __launch_bounds__(64) void final_kernel(const u64* __restrict__ p, in
 
 // -- host ----------------------------------------------------------------------------------------------------------------------------
 
-struct Fmt {
-    bool il;
-    int bits, sh, sx, sy;
-};
-
-bool format_of(int layout, int bits, int shift, int sx, int sy, Fmt& f)
-{
-    if (layout != PC_CHR_PLANAR && layout != PC_CHR_SEMIPLANAR) return false;
-    if (!((bits == 8 && shift == 0) || (bits == 10 && (shift == 0 || shift == 6)))) return false;
-    if (!((sx == 2 && sy == 2) || (sx == 2 && sy == 1) || (sx == 1 && sy == 1))) return false;
-    f = Fmt{layout == PC_CHR_SEMIPLANAR, bits, shift, sx, sy};
-    return true;
-}
-
-bool site_ok(int s) { return s == PC_CHR_CENTRE || s == PC_CHR_COSITED; }
-
-// the levels are those of the shared header for the depth: NV12's for 8 bits, P010's for 10
-bool depth_levels(int bits, int range, Levels& lv) { return levels_of(bits == 10 ? PC_YUV_P010 : PC_YUV_NV12, range, lv); }
-
-// One picture of W luma columns in format f; the batch strides are not looked at.
-bool picture_ok(const Fmt& f, const pc_chr_frame* fr, int W)
-{
-    if (!fr) return false;
-    const int es = f.bits == 10 ? 2 : 1;
-    const int64_t Wc = cdiv(W, f.sx);
-    if (!plane_ok(fr->y, fr->y_row, es, W)) return false;
-    if (f.il) return plane_ok(fr->u, fr->u_row, es, 2 * Wc);
-    return plane_ok(fr->u, fr->u_row, es, Wc) && plane_ok(fr->v, fr->v_row, es, Wc);
-}
-
 // The item space: SY rows by eight columns, T * T / (8 SY) items to a tile, NT to a block.  Blocks per tile and blocks in all;
 // false for what the calls refuse.
 bool item_blocks_of(int T, int sy, int n_tiles, int t_max, int& bpt, int64_t& blocks)
@@ -285,25 +252,6 @@ bool wide_path(const void* x, int64_t st, int64_t sc, int64_t sh, int O, bool il
     if (!f32_wide(x, st, sc, sh) || (sx == 2 && O % 8 != 0)) return false;
     if (!plane_wide(ref->y, ref->y_row, es) || !plane_wide(ref->u, ref->u_row, es)) return false;
     return il || plane_wide(ref->v, ref->v_row, es);
-}
-
-template <int N>
-using Int = std::integral_constant<int, N>;
-
-// f(element, interleaved, SX, SY) with the format's compile-time values
-template <class F>
-void with_format(const Fmt& fm, F f)
-{
-    auto sub = [&](auto el, auto il) {
-        if (fm.sy == 2) f(el, il, Int<2>{}, Int<2>{});
-        else if (fm.sx == 2) f(el, il, Int<2>{}, Int<1>{});
-        else f(el, il, Int<1>{}, Int<1>{});
-    };
-    if (fm.bits == 8) {
-        if (fm.il) sub(uint8_t{}, std::true_type{}); else sub(uint8_t{}, std::false_type{});
-    } else {
-        if (fm.il) sub(uint16_t{}, std::true_type{}); else sub(uint16_t{}, std::false_type{});
-    }
 }
 
 }  // namespace

@@ -2,7 +2,7 @@
 (tests/chroma_clips_contract.py against tests/chroma_tiles_contract.cut and tests/chroma_contract.taps, and against
 tests/clips_contract.py for centre-sited 4:2:0); the PCL1 container up to the model; encode and decode against fake models;
 libpc_chroma_clips.so's C ABI up to the first device call; progressivecodec_amd.chroma_clips' argument checks; the structure of the
-fifteenth library, its restated ingest item and the ledger of its kernels."""
+fifteenth library and the ledger of its kernels."""
 import ctypes as C
 import glob
 import inspect
@@ -24,7 +24,6 @@ from tests import frames_contract as FC
 from tests import image_shared
 from tests import tiles_contract as TC
 from tests.test_chroma_host import fake_frame
-from tests.test_chroma_tiles_host import function_body
 from tests.test_image_shared_host import DEFINITIONS
 from tests.test_tiles_host import blob
 
@@ -38,6 +37,19 @@ def _lib():
     """the module and its library; a library that is not built is an ImportError, as for every other one"""
     from progressivecodec_amd import chroma_clips
     return chroma_clips, chroma_clips.lib()
+
+
+def function_body(text, name):
+    """the text between the braces of the definition of `name` (the first `name(` that is followed by a body)"""
+    m = re.search(r"\bvoid %s\(" % name, text)
+    assert m, name
+    start = text.index("{", text.index(")\n{", m.end()))
+    depth = 0
+    for i in range(start, len(text)):
+        depth += {"{": 1, "}": -1}.get(text[i], 0)
+        if depth == 0:
+            return text[start + 1:i]
+    raise AssertionError("unbalanced braces")
 
 
 def same_bits(a, b):
@@ -670,8 +682,9 @@ def test_the_fifteenth_library_keeps_the_rules_of_the_fourteen():
         assert other not in code, other
     for name, pattern in DEFINITIONS.items():
         assert not re.search(pattern, code), name
-    shared = ("HIPCHK", "g_last_hip", "Planes", "planes_of", "load4", "store8", "Levels", "levels_of", "IngestCoef", "to_rgb", "clampi",
-              "block_reduce", "row_final", "plane_wide", "plane_ok", "aligned", "upsample_ok", "cdiv", "Grid", "geo_of", "NT", "COLS", "Sum")
+    shared = ("HIPCHK", "g_last_hip", "Planes", "planes_of", "load4", "store8", "Levels", "IngestCoef",
+              "block_reduce", "row_final", "plane_wide", "aligned", "upsample_ok", "cdiv", "Grid", "geo_of", "NT", "COLS", "Sum",
+              "ingest_item", "Taps", "taps_of", "code_of", "Fmt", "format_of", "with_format", "picture_ok", "site_ok", "depth_levels")
     for name in shared:
         assert re.search(r"\b%s\b" % name, code), name
         assert not re.search(r"\b(struct|void|int|bool|unsigned|float|define|constexpr int)\s+%s\b\s*[({=]" % name, code), name
@@ -682,6 +695,11 @@ def test_the_fifteenth_library_keeps_the_rules_of_the_fourteen():
     values = dict((k, int(v)) for k, v in re.findall(r"\b(PC_CHC_\w+) = (\d+)", hdr))
     assert values == {"PC_CHC_PLANAR": chroma.PLANAR, "PC_CHC_SEMIPLANAR": chroma.SEMIPLANAR, "PC_CHC_CENTRE": chroma.CENTRE,
                       "PC_CHC_COSITED": chroma.COSITED, "PC_CHC_CHANGES": kc.CHANGES, "PC_CHC_CUT": kc.CUT}
+    # the cut kernel differs from pc_chroma_tiles.hip's cut_kernel in where the tile comes from alone: the same item (the shared header's),
+    # the same guard, the same stores
+    theirs = open(os.path.join(PKG, "chroma_tiles_hip", "pc_chroma_tiles.hip")).read()
+    for line in ("if (item >= items) return;", "ingest_item<T, IL, SX, SY, WIDE>(s, W, Hc, Wc, (int)Y64, (int)X64, t, lv, k, o);", "store8<WIDE>(dst + ("):
+        assert line in function_body(src, "cut_list_kernel") and line in function_body(theirs, "cut_kernel")
     # plain C++: no inline assembly, no builtins, no atomics, no LDS of its own
     assert not re.search(r"\batomic(Add|CAS|Exch|Max|Min|Or|And)\b|\basm\b|__asm|__shared__|__syncthreads|__builtin_|__shfl", code)
     import bench
@@ -695,25 +713,6 @@ def test_the_fifteenth_library_keeps_the_rules_of_the_fourteen():
     assert "clips._decode(" in text and "window_of=" in text and "covering_of=" in text and "decode_positions" not in inspect.getsource(kc)
     params = inspect.signature(clips._decode).parameters
     assert params["window_of"].default is None and params["covering_of"].default is None
-
-
-def test_the_restated_item_is_pc_chroma_tiles_hips():
-    """pc_chroma_tiles.hip cannot share its item through a header yet (its own tests pin its text): until it can, the copy may not
-    drift"""
-    norm = lambda s: re.sub(r"\s+", " ", re.sub(r"//[^\n]*", "", s)).strip()                     # noqa: E731
-    ours = open(os.path.join(DIR, "pc_chroma_clips.hip")).read()
-    theirs = open(os.path.join(PKG, "chroma_tiles_hip", "pc_chroma_tiles.hip")).read()
-    a, b = function_body(ours, "ingest_item"), function_body(theirs, "ingest_item")
-    assert len(norm(b)) > 3000 and norm(a) == norm(b)
-    sig = lambda t: norm(t[t.index("template <class T, bool IL, int SX, int SY, bool WIDE>\n__device__"):t.index("{", t.index("void ingest_item("))])  # noqa: E731
-    assert sig(ours) == sig(theirs)
-    for name in ("code_of", "word_of"):
-        pat = r"template <class T>\n__device__ __forceinline__ unsigned %s\([^\n]*\n" % name
-        assert re.search(pat, ours).group(0) == re.search(pat, theirs).group(0)
-    assert norm(re.search(r"struct Taps \{.*?\};", ours, re.S).group(0)) == norm(re.search(r"struct Taps \{.*?\};", theirs, re.S).group(0))
-    # and the cut kernel around it differs from cut_kernel in where the tile comes from alone: the same guard, the same stores
-    for line in ("if (item >= items) return;", "store8<WIDE>(dst + ("):
-        assert line in function_body(ours, "cut_list_kernel") and line in function_body(theirs, "cut_kernel")
 
 
 # -- 6. the ledger -------------------------------------------------------------------------------------------------------------------

@@ -572,8 +572,9 @@ def test_the_twelfth_library_keeps_the_rules_of_the_eleven():
     assert '#include "pc_image_host.h"' in src
     for name, pattern in DEFINITIONS.items():
         assert not re.search(pattern, code), name
-    shared = ("HIPCHK", "g_last_hip", "Planes", "load4", "store4", "store8", "Levels", "levels_of", "IngestCoef", "EmitCoef", "to_rgb",
-              "emit_px", "clampi", "block_reduce", "gather_partials", "plane_wide", "f32_wide", "upsample_ok", "cdiv", "F32")
+    shared = ("HIPCHK", "g_last_hip", "Planes", "load4", "store4", "store8", "Levels", "IngestCoef", "EmitCoef",
+              "emit_px", "clampi", "block_reduce", "gather_partials", "plane_wide", "f32_wide", "upsample_ok", "cdiv", "F32",
+              "ingest_item", "Taps", "taps_of", "code_of", "word_of", "Fmt", "format_of", "with_format", "site_ok", "depth_levels")
     for name in shared:
         assert re.search(r"\b%s\b" % name, code), name
         assert not re.search(r"\b(struct|void|int|bool|unsigned|float|define)\s+%s\b\s*[({]" % name, code), name

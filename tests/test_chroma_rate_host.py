@@ -377,8 +377,9 @@ def test_the_fourteenth_library_keeps_the_rules_of_the_thirteen():
         assert other not in code, other
     for name, pattern in DEFINITIONS.items():
         assert not re.search(pattern, code), name
-    shared = ("HIPCHK", "g_last_hip", "Planes", "planes_of", "load4", "Levels", "levels_of", "EmitCoef", "emit_px", "clampi", "block_reduce",
-              "row_final", "plane_wide", "plane_ok", "f32_wide", "cdiv", "aligned", "F32", "Grid", "Geo", "geo_of", "axis_weight", "NT", "COLS", "Sum")
+    shared = ("HIPCHK", "g_last_hip", "Planes", "planes_of", "load4", "Levels", "EmitCoef", "emit_px", "clampi", "block_reduce",
+              "row_final", "plane_wide", "f32_wide", "aligned", "F32", "Grid", "Geo", "geo_of", "axis_weight", "NT", "COLS", "Sum",
+              "code_of", "Fmt", "format_of", "with_format", "picture_ok", "site_ok", "depth_levels")
     for name in shared:
         assert re.search(r"\b%s\b" % name, code), name
         assert not re.search(r"\b(struct|void|int|bool|unsigned|float|define|constexpr int)\s+%s\b\s*[({=]" % name, code), name

@@ -17,6 +17,18 @@ DEFINITIONS = {
     "geo_of": r"\bbool geo_of\(",
     "axis_tiles": r"\bint64_t axis_tiles\(",
     "define HIPCHK": r"#\s*define HIPCHK\b",
+    # image_csrc/pc_chroma_items.h: what the libraries of the twelve formats share
+    "ingest_item": r"\bvoid ingest_item\(",
+    "struct Taps": r"\bstruct Taps \{\s*int\b",           # the ingest's integer weights; pc_metrics.hip's Taps is a window of floats
+    "code_of": r"\bunsigned code_of\(",
+    "word_of": r"\bunsigned word_of\(",
+    "struct Fmt": r"\bstruct Fmt\b",
+    "format_of": r"\bbool format_of\(",
+    "with_format": r"\bvoid with_format\(",
+    "axis_taps": r"\bvoid axis_taps\(",
+    "picture_ok": r"\bbool picture_ok\(",
+    "site_ok": r"\bbool site_ok\(",
+    "depth_levels": r"\bbool depth_levels\(",
 }
 
 YUV_LIBS = {"frames": "PC_FRAMES", "frame_tiles": "PC_FT", "frame_rate": "PC_FR", "clips": "PC_CL", "clip_rate": "PC_CR", "clip_tol": "PC_CT"}
@@ -30,14 +42,21 @@ def _code(path):
 def test_shared_names_are_defined_once_under_image_csrc():
     shared = {p: _code(p) for p in glob.glob(os.path.join(PKG, "image_csrc", "*.h"))}
     sources = sorted(glob.glob(os.path.join(PKG, "*_csrc", "*.hip")))
-    assert len(sources) == len(LIBS) and not glob.glob(os.path.join(PKG, "image_csrc", "*.hip"))
+    assert len(sources) == len(LIBS) == 10 and not glob.glob(os.path.join(PKG, "image_csrc", "*.hip"))
+    # every library's source: the ten, and the later ones whose directories the pins of the ten do not count
+    later = sorted(glob.glob(os.path.join(PKG, "*_hip", "*.hip"))) + sorted(glob.glob(os.path.join(PKG, "chroma_clips_kernels", "*.hip")))
+    assert [os.path.basename(p) for p in later] == ["pc_chroma.hip", "pc_chroma_rate.hip", "pc_chroma_tiles.hip", "pc_clip_tol_rate.hip",
+                                                    "pc_chroma_clips.hip"]
     for name, pattern in DEFINITIONS.items():
         homes = [p for p, txt in shared.items() if re.search(pattern, txt)]
         assert len(homes) == 1, (name, homes)
-        for src in sources:
+        for src in sources + later:
             assert not re.search(pattern, _code(src)), (name, src)
+    # code_of had a second name in pc_chroma_rate.hip; it is gone, from the headers too
+    for path in sources + later + list(shared):
+        assert not re.search(r"\bcode_in\b", open(path).read()), path
     # and every library's source reaches them through the host header
-    for src in sources:
+    for src in sources + later:
         assert '#include "pc_image_host.h"' in open(src).read(), src
 
 
