@@ -35,8 +35,9 @@ coded in: two entries are either equal or disjoint, anything else is refused.  A
 is asked for, so a clip cut off inside its payload still gives every frame whose tiles it holds completely.
 
 There is no CPU fallback: CPU tensors raise ValueError before any device call.  Everything runs on the current stream of the tensors'
-device.  Out of scope: a tolerance, rate control over a clip and anything else above this layer (what clip_tol.py, clip_rate.py and
-clip_tol_rate.py are to clips.py), any inter-frame prediction.
+device.  Rate control over a clip is the layer above this one (chroma_clip_rate.py, DESIGN.md section 28: what clip_rate.py is to
+clips.py).  Out of scope: a tolerance and anything else above this layer (what clip_tol.py and clip_tol_rate.py are to clips.py), any
+inter-frame prediction.
 """
 import ctypes as C
 import struct

@@ -22,7 +22,8 @@ differ in those samples and nowhere else; ChromaRatePlan.sse_exact says which ca
 distortion depend on the neighbour's level, and the allocator needs it not to.
 
 There is no CPU fallback: CPU tensors raise ValueError before any device call.  Everything runs on the current stream of the tensor's
-device.  Out of scope: clips on these formats (the layers after this one, as sections 16 to 18 and 20 follow section 15), a target
+device.  A clip of these frames in at most N bytes is chroma_clip_rate.py (section 28, over chroma_clips.py's section 25: the same
+measure for a list of (frame, tile) jobs).  Out of scope: a tolerance on clips of these formats (as sections 18 and 20), a target
 PSNR, measuring in an output format other than the stored one, batches of frames.
 """
 import collections

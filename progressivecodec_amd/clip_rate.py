@@ -26,7 +26,8 @@ level; tiles may differ in quality.  What PCT2 is to PCT1.
 There is no CPU fallback: CPU tensors raise ValueError before any device call.  Everything runs on the current stream of the tensors'
 device.  Out of scope: per-frame byte caps and constant bitrate, a target PSNR (the dual problem), a tolerance inside
 encode_clip_to_size (the reuse identity above does not hold under it: clip_tol_rate.py is that encoder), inter-frame
-prediction, batching the decode across frames.
+prediction, batching the decode across frames.  The same layer for the twelve formats and three sitings of `chroma` is
+chroma_clip_rate.py (section 28); it comes through _to_size_arguments and _allocate_and_pack below with its own checks and packer.
 """
 import collections
 import ctypes as C
@@ -221,28 +222,32 @@ def item_weights(items, runs, n_tiles, n_frames, importance=None, frame_weights=
 # -- through the codec ---------------------------------------------------------------------------------------------------------------
 
 def _to_size_arguments(frames, qualities, target_bytes, fmt, matrix, range, upsample, tile, overlap, plane_weights, importance, frame_weights,
-                       max_tiles_per_call):
+                       max_tiles_per_call, check_enums=None, clip_frames=None, grid=None):
     """the argument checks of encode_clip_to_size (clip_tol_rate.encode_clip_to_size comes here, too), in its order and with its
     messages -> (qualities, step, plane weights, target_bytes, fs (the planes of frame k as batched views), the grid, importance
-    flat or None, frame_weights as a list or None)"""
+    flat or None, frame_weights as a list or None).  The three keywords are for a caller with other formats (chroma_clip_rate.py):
+    check_enums(fmt, matrix, range, upsample), clip_frames(frames, fmt) and grid(H, W, tile, overlap); by default the 4:2:0 checks,
+    clips._clip_frames and clips._grid."""
     qualities = _tilecodec.levels_of(qualities)
-    _check_enums(fmt, matrix, range, upsample)
+    (check_enums or _check_enums)(fmt, matrix, range, upsample)
     step = _tilecodec.tiles_per_call(max_tiles_per_call)
     pw = _tilecodec.plane_weights_of(plane_weights)
     target_bytes = int(target_bytes)
-    fs, H, W = _clip_frames(frames, fmt)
-    g = clips._grid(H, W, tile, overlap)
+    fs, H, W = (clip_frames or _clip_frames)(frames, fmt)
+    g = (grid or clips._grid)(H, W, tile, overlap)
     _tilecodec.tile_limit(g.T, fmt)
     return qualities, step, pw, target_bytes, fs, g, _tilecodec.importance_of(importance, g), _tilecodec.frame_weights_of(frame_weights, len(fs))
 
 
-def _allocate_and_pack(bufs, dists, weights, items, source, target_bytes, g, fmt, matrix, range, upsample):
+def _allocate_and_pack(bufs, dists, weights, items, source, target_bytes, g, fmt, matrix, range, upsample, header_bytes=None, pack=None):
     """What follows the work loop of encode_clip_to_size (and of clip_tol_rate's): bufs[i][l] the single-level containers of item
     i, dists[i][l] what each level leaves -> (the PCS2 container of at most target_bytes bytes, levels[i], rates[i][l]).
-    ValueError, its message holding the minimum, if the cheapest level of every item does not fit."""
+    ValueError, its message holding the minimum, if the cheapest level of every item does not fit.  The two keywords are for a
+    caller with another container (chroma_clip_rate.py's PCL2): the bytes of its header and its packer, called with pack_clip's
+    arguments; by default PCS2's 42 bytes and pack_clip."""
     n, F = g.ny * g.nx, len(source)
     rates = [[len(p) for p in row] for row in bufs]
-    fixed = HEADER_BYTES + ENTRY_BYTES * F * n
+    fixed = (HEADER_BYTES if header_bytes is None else header_bytes) + ENTRY_BYTES * F * n
     minimum = sum(min(r) for r in rates)
     if fixed + minimum > target_bytes:
         raise ValueError(f"target_bytes = {target_bytes} is below the minimum of {fixed + minimum} bytes: {fixed} bytes of header and table "
@@ -251,7 +256,7 @@ def _allocate_and_pack(bufs, dists, weights, items, source, target_bytes, g, fmt
     blobs = [[None] * n for _ in _range(F)]
     for (f, t), row, l in zip(items, bufs, levels):
         blobs[f][t] = row[l]
-    return pack_clip(blobs, source, g.H, g.W, g.T, g.O, fmt, matrix, range, upsample), levels, rates
+    return (pack or pack_clip)(blobs, source, g.H, g.W, g.T, g.O, fmt, matrix, range, upsample), levels, rates
 
 
 def encode_clip_to_size(model, frames, qualities, target_bytes, fmt, matrix="bt709", range="limited", upsample="linear", tile=512,
