@@ -36,8 +36,9 @@ is asked for, so a clip cut off inside its payload still gives every frame whose
 
 There is no CPU fallback: CPU tensors raise ValueError before any device call.  Everything runs on the current stream of the tensors'
 device.  Rate control over a clip is the layer above this one (chroma_clip_rate.py, DESIGN.md section 28: what clip_rate.py is to
-clips.py).  Out of scope: a tolerance and anything else above this layer (what clip_tol.py and clip_tol_rate.py are to clips.py), any
-inter-frame prediction.
+clips.py).  A tolerance for near-static tiles is the other layer above this one (chroma_clip_tol.py, DESIGN.md section 29: what
+clip_tol.py is to clips.py).  Out of scope: a tolerance under a byte budget (what clip_tol_rate.py is to clips.py), any inter-frame
+prediction.
 """
 import ctypes as C
 import struct
@@ -289,6 +290,19 @@ def _source(fs, fmt, siting, g, upsample, reuse):
     return [[f] * n for f in _range(F)]
 
 
+def _encode_source(model, fs, g, source, qualities, fmt, matrix, range, upsample, siting, mask_pol, step):
+    """encode_clip once the source table is known (chroma_clip_tol.encode_clip comes here with its own): fs[k] the planes of frame k as
+    batched views, everything checked -> (the PCL1 container, the number of coded tiles).  The work list -- every (f, t) with
+    source[f][t] == f, in (f, t) order -- is chunked by `step` across frames (_tilecodec.encode_items over _cut_of's cut)."""
+    n, F = g.ny * g.nx, len(fs)
+    work = [(f, t) for f in _range(F) for t in _range(n) if source[f][t] == f]
+    bufs = _tilecodec.encode_items(model, len(work), step, qualities, mask_pol, g.T, _cut_of(fs, g, work, fmt, matrix, range, upsample, siting))
+    blobs = [[None] * n for _ in _range(F)]
+    for (f, t), b in zip(work, bufs):
+        blobs[f][t] = b
+    return pack_clip(blobs, source, g.H, g.W, g.T, g.O, fmt, matrix, range, upsample, siting), len(work)
+
+
 def encode_clip(model, frames, qualities, fmt, matrix="bt709", range="limited", upsample="linear", siting="centre", tile=512, overlap=0,
                 mask_pol="point-based-std", reuse=True, max_tiles_per_call=32):
     """clip -> (PCL1 container (bytes), ClipPlan) holding every level of `qualities` for every tile of every frame.  With reuse, one
@@ -305,13 +319,8 @@ def encode_clip(model, frames, qualities, fmt, matrix="bt709", range="limited", 
     g = _grid(H, W, tile, overlap)
     n, F = g.ny * g.nx, len(fs)
     source = _source(fs, fmt, siting, g, upsample, reuse)
-    work = [(f, t) for f in _range(F) for t in _range(n) if source[f][t] == f]
-    bufs = _tilecodec.encode_items(model, len(work), step, qualities, mask_pol, g.T, _cut_of(fs, g, work, fmt, matrix, range, upsample, siting))
-    blobs = [[None] * n for _ in _range(F)]
-    for (f, t), b in zip(work, bufs):
-        blobs[f][t] = b
-    buf = pack_clip(blobs, source, g.H, g.W, g.T, g.O, fmt, matrix, range, upsample, siting)
-    return buf, ClipPlan(source, len(work), F * n - len(work), len(buf))
+    buf, n_coded = _encode_source(model, fs, g, source, qualities, fmt, matrix, range, upsample, siting, mask_pol, step)
+    return buf, ClipPlan(source, n_coded, F * n - n_coded, len(buf))
 
 
 def decode_clip(model, buf, frames=None, level=-1, region=None, fmt=None, siting=None, max_tiles_per_call=32):

@@ -27,7 +27,8 @@ every tile is coded (reuse=False).
 There is no CPU fallback: CPU tensors raise ValueError before any device call.  Everything runs on the current stream of the tensors'
 device.  Out of scope: a tolerance inside clip_rate.encode_clip_to_size (its reuse identity D(k, t) = D(f, t) does not hold for a
 tile that is only close; clip_tol_rate.encode_clip_to_size measures every frame of a run and is that encoder),
-inter-frame prediction, matching a tile against other tiles, 4:2:2 / 4:4:4.
+inter-frame prediction, matching a tile against other tiles.  4:2:2 / 4:4:4 and left- / top-left-sited frames: chroma_clip_tol.py
+(DESIGN.md section 29), this module for the twelve formats and three sitings of `chroma`.
 """
 import collections
 import ctypes as C
