@@ -74,7 +74,7 @@ ORC_API int orc_rans_encode(const int32_t *sym, const int32_t *idx, int64_t n,
         PUSH(c[value], c[value + 1] - c[value], 0);              /* :133-135 */
         if (value == max_value) {                                /* :138-162 */
             int32_t n_bypass = 0;
-            while ((raw >> (n_bypass * BYPASS_BITS)) != 0) ++n_bypass;
+            while (n_bypass < 8 && (raw >> (n_bypass * BYPASS_BITS)) != 0) ++n_bypass;   /* raw >= 2^28: a shift by 32 is undefined (x86 never ends the loop) */
             int32_t val = n_bypass;
             while (val >= BYPASS_MAX) { PUSH(BYPASS_MAX, BYPASS_MAX + 1, 1); val -= BYPASS_MAX; }
             PUSH(val, val + 1, 1);

@@ -19,11 +19,7 @@ import torch.nn.functional as F
 pytestmark = pytest.mark.gpu
 
 from oracle.codec_ref import bpp_of, compute_padding, psnr_of  # noqa: E402
-from tests.util import e2e_cases, gpu_codec, inputs, oracle_codec  # noqa: E402
-
-NORTH_STAR_PSNR_TOL_DB = 1e-4   # BASELINE.json north_star: "reconstructed pixels within 1e-4 dB PSNR" -- asserted on every flip-free case
-PSNR_TOL_DB = 2e-3      # cases in which float rounding flipped a symbol against the PyTorch reference (reported one by one)
-BPP_TOL = 2e-3
+from tests.util import BPP_TOL, LIK_RTOL, NORTH_STAR_PSNR_TOL_DB, PSNR_TOL_DB, e2e_cases, gpu_codec, inputs, oracle_codec  # noqa: E402
 
 
 def sha(b):
@@ -342,7 +338,6 @@ def test_harness_shared_base_gives_the_same_rd_table():
 
 
 # ------------------------------------------------------------------ likelihood path
-LIK_RTOL = 3e-7     # one float32 ulp: the HIP kernel and the oracle round a double erfc from different libms (ocml / scipy)
 
 
 @pytest.mark.parametrize("case", [(2, 64, 64, 11, "rand", 0), (2, 64, 64, 11, "rand", 0.5), (1, 128, 128, 12, "smooth", 2), (1, 64, 192, 13, "rand", 10)])

@@ -10,6 +10,12 @@ import torch.nn.functional as F
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden")
 
+# tolerances against the real reference's goldens, shared by every test that compares with them
+NORTH_STAR_PSNR_TOL_DB = 1e-4   # BASELINE.json north_star: "reconstructed pixels within 1e-4 dB PSNR" -- asserted on every flip-free case
+PSNR_TOL_DB = 2e-3      # cases in which float rounding flipped a symbol against the PyTorch reference (reported one by one)
+BPP_TOL = 2e-3
+LIK_RTOL = 3e-7     # one float32 ulp: the HIP kernel and the oracle round a double erfc from different libms (ocml / scipy)
+
 
 def inputs(B, H, W, seed, kind="rand"):
     """Identical to tests/golden/make_golden.py:inputs."""
