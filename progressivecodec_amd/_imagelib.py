@@ -10,7 +10,7 @@ that links no other.  The thirteen modules that shared this when it was written:
 
 and since then also:
 
-  chroma_rate, chroma_clips, chroma_clip_rate, chroma_clip_tol
+  chroma_rate, chroma_clips, chroma_clip_rate, chroma_clip_tol, chroma_clip_tol_rate
 """
 import ctypes as C
 import os

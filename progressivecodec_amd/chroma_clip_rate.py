@@ -29,8 +29,9 @@ PCL2 is PCL1 (chroma_clips.py: the 47-byte header, PCS1's table and payload rule
 container holding EXACTLY ONE level; tiles may differ in quality.  What PCS2 is to PCS1.
 
 There is no CPU fallback: CPU tensors raise ValueError before any device call.  Everything runs on the current stream of the tensors'
-device.  Out of scope: a tolerance (what clip_tol.py and clip_tol_rate.py are to clips.py: the next two layers), measuring all levels
-of a chunk in one launch, per-frame byte caps, a target PSNR, inter-frame prediction.
+device.  A tolerance for near-static tiles under the same budget is the layer above this one (chroma_clip_tol_rate.py, DESIGN.md
+section 30: what clip_tol_rate.py is to clip_rate.py).  Out of scope: measuring all levels of a chunk in one launch, per-frame byte
+caps, a target PSNR, inter-frame prediction.
 """
 import collections
 import ctypes as C

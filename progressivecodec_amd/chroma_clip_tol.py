@@ -28,8 +28,8 @@ anchor[t] = k.  stats[0] is all zeros.  With the all-zero tolerance and no max_r
 max_run = 1 every tile is coded (reuse=False).  For "nv12", "i420" and "p010" at "centre" everything is clip_tol's, bit for bit.
 
 There is no CPU fallback: CPU tensors raise ValueError before any device call.  Everything runs on the current stream of the tensors'
-device.  Out of scope: a tolerance inside chroma_clip_rate.encode_clip_to_size (what clip_tol_rate.py is to clip_rate.py: the next
-layer), inter-frame prediction, matching a tile against other tiles.
+device.  The same tolerance under a byte budget is the layer above this one (chroma_clip_tol_rate.py, DESIGN.md section 30: what
+clip_tol_rate.py is to clip_rate.py).  Out of scope: inter-frame prediction, matching a tile against other tiles.
 """
 import ctypes as C
 
